@@ -20,7 +20,11 @@ What is printed (round 5): the LAST line of stdout is a SHORT record (short_line
 `cpu_baseline` and the headline numbers of the legs below; the whole record (prose, per-leg records, worker reports) goes to bench_detail.json next to this file (and under
 gpurun_out/ when that exists), a few human lines to stderr.
 
-Keys of the N=1 record (each measured after the timed region, none inside it):
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) generates and uploads the bin set, warms up, times the N steps and prints the line: the keys below, the
+output digest and the oracle check of the timed run's bins are measured only under --full. --dump-outputs DIR writes what the last timed step computed
+(dump_outputs(): tallies, per-bin tallies, a seeded sample of the records and LUTs) as .npy files, so that two builds can be compared output for output.
+
+Keys of the N=1 record under --full (each measured after the timed region, none inside it):
   value_two_streams   : the same step with two bins in flight (tails and launch gaps of one bin filled by the other)
   value_host_boundary : the same bins from pinned host memory (PCIe inclusive) through kmc_hip_process_bin_submit/_wait (one bin per call) and through
                         kmc_hip_process_bins_submit/_wait (4 bins per call): the better of the two, both in host_boundary.legs
@@ -323,6 +327,45 @@ def oracle_check(ctx, w, res, n_check=16):
     for t in th:
         t.join()
     return verdicts
+
+
+DUMP_RECORD_BYTES = 48 << 20  # --dump-outputs: the records sample stays below this (float32 per byte), the LUT sample below DUMP_LUT_BYTES
+DUMP_LUT_BYTES = 8 << 20
+
+
+def dump_outputs(ctx, w, res, tallies, directory):
+    """--dump-outputs: what the last timed step computed, as a caller of kmc_hip_process_bins_device receives it, for this rank's bins in their order:
+      tallies.npy         float64 [4]            n_unique, n_cutoff_min, n_cutoff_max, n_total over all ranks
+      bin_ids.npy         float64 [bins]         bin number of every row below
+      bin_stats.npy       float64 [bins, 5]      the bin's four tallies and the bytes of (suffix, counter) records it wrote
+      records_sample.npy  float32 [bins, S, R]   S consecutive output records of R bytes (byte values) from a seeded offset in each bin; -1 past a bin's end
+      lut_sample.npy      float64 [bins, L]      the bin's LUT (prefix -> first record) at L seeded indices, the same for every bin
+    The sample positions depend only on the bin set and the seed, so equal arguments give equal files for equal results."""
+    os.makedirs(directory, exist_ok=True)
+    n, R = w.n_own, w.rec_bytes
+    rng = np.random.default_rng(SEED)
+    S = int(max(1, min(512, DUMP_RECORD_BYTES // max(1, n * R * 4))))
+    L = int(max(1, min(512, w.lut_n, DUMP_LUT_BYTES // max(1, n * 8)))) if w.lut_n else 0
+    lut_idx = np.sort(rng.choice(w.lut_n, size=L, replace=False)) if L else np.zeros(0, dtype=np.int64)
+    recs = np.full((n, S, R), -1.0, dtype=np.float32)
+    luts = np.zeros((n, L), dtype=np.float64)
+    lut = np.zeros(max(w.lut_n, 1), dtype=np.uint64)
+    for i in range(n):
+        n_out = int(res[i, 4]) // R
+        start = int(rng.integers(0, max(n_out - S, 0) + 1))
+        m = min(S, n_out - start)
+        if m > 0:
+            buf = np.zeros(m * R, dtype=np.uint8)
+            ctx.d2h(buf, w.d_out + w.out_off[i] + start * R)
+            recs[i, :m] = buf.reshape(m, R)
+        if L:
+            ctx.d2h(lut[: w.lut_n], w.d_lut + w.lut_n * 8 * i)
+            luts[i] = lut[lut_idx]
+    np.save(os.path.join(directory, "tallies.npy"), np.asarray(tallies, dtype=np.float64))
+    np.save(os.path.join(directory, "bin_ids.npy"), np.array([b[0] for b in w.bins], dtype=np.float64))
+    np.save(os.path.join(directory, "bin_stats.npy"), res[:n, :5].astype(np.float64))
+    np.save(os.path.join(directory, "records_sample.npy"), recs)
+    np.save(os.path.join(directory, "lut_sample.npy"), luts)
 
 
 # ---------------------------------------------------------------------------------------------------------------- logical devices
@@ -814,7 +857,7 @@ def e2e_large_leg(ctx, k: int, gbp: float, budget_s: float = 1500.0):
 def secondary_leg(name: str, k: int, extra, env=None):
     cfg = CONFIGS[name]
     cmd = [sys.executable, os.path.abspath(__file__), "--leg", name, "--k", str(k), "--reads", str(cfg["reads"]), "--genome", str(cfg["genome"]),
-           "--bins", str(cfg["bins"]), "--steps", "3", "--warmup", "1", *extra]
+           "--bins", str(cfg["bins"]), "--steps", "3", "--warmup", "1", "--full", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, **env) if env else None)
     for ln in reversed(r.stdout.splitlines()):
         if ln.startswith("{"):
@@ -867,7 +910,16 @@ def main():
     ap.add_argument("--e2e-gbp", type=float, default=8.0, help="size of the e2e_large leg's FASTQ in Gbp (0 = skip; 30 = the full configs[2] shape, ~4 minutes more)")
     ap.add_argument("--also-two-streams", action="store_true", help="secondary legs: time the step with two groups in flight as well (value_two_streams)")
     ap.add_argument("--dry-launch", action="store_true", help="launcher check (runs without a GPU): start the ranks --gpus asks for, rendezvous over gloo, print what they see")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: output digest, oracle check, two streams, host boundary, secondary legs, "
+                                                         "CPU baselines, e2e legs (a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps: what the last step computed (rank 0's bins) as DIR/<name>.npy, float32/float64, "
+                                                                     "a fixed seeded sample of the records and LUTs (< 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: only what the headline figure needs (the legs after the timed region are skipped below)
+        args.no_digest = args.no_oracle_check = args.no_host_boundary = True
+        args.also_two_streams = False
 
     # `python bench.py --gpus N` with no launcher around it starts its own N ranks (one process per GPU, rendezvous on 127.0.0.1): the same command
     # line re-executed under torch.distributed.run. Under a launcher (the driver's `python -m torch.distributed.run ... bench.py --gpus N`) WORLD_SIZE
@@ -887,6 +939,18 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"bench.py --gpus {args.gpus} was started with WORLD_SIZE={world}: the launcher's ranks and --gpus must agree")
+    # one rank: the bin set is generated (C threads, GIL released) while torch and the HIP runtime start up
+    pre = {}
+    if world == 1 and not args.dry_launch:
+        def _generate():
+            try:
+                pre["sb"] = sharding.generate_sharded_bins(SEED, args.genome, args.reads, args.k, args.bins, 0, 1, max(2, 2 * sharding.effective_cpus()),
+                                                           cache_dir=args.cache or None)
+            except BaseException as e:  # noqa: BLE001 — raised again where the bins are needed
+                pre["error"] = e
+
+        pre["thread"] = threading.Thread(target=_generate, daemon=True)
+        pre["thread"].start()
     import torch
 
     if args.dry_launch:
@@ -944,7 +1008,13 @@ def main():
     pl = args.lut_prefix if args.lut_prefix >= 0 else kmc_lut_prefix_len(k, args.reads, args.bins)
     p = capi.make_params(k, lut_prefix_len=pl)
     want_host = is_main and world == 1 and not args.no_host_boundary
-    w = build_workload(ctx, args, k, p, rank, world, keep_host=want_host)
+    sb = None
+    if pre:
+        pre["thread"].join()
+        if "error" in pre:
+            raise pre["error"]
+        sb = pre["sb"]
+    w = build_workload(ctx, args, k, p, rank, world, keep_host=want_host, sb=sb)
 
     for _ in range(args.warmup):
         run_step(ctx, w, args.streams)
@@ -982,6 +1052,8 @@ def main():
         sc = torch.tensor([float(n_launch), sc_ms, float(sc_recs)], dtype=torch.float64, device=dev)
         dist.all_reduce(sc)
         n_launch, sc_ms, sc_recs = int(sc[0].item()), float(sc[1].item()), int(sc[2].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, w, res, tallies, args.dump_outputs)
 
     # ---- self-checks on the timed run's own output (every rank)
     rec_bytes = w.rec_bytes
@@ -1122,8 +1194,8 @@ def main():
             out["value_two_streams"] = w.total_kmers_all * 2 / (time.perf_counter() - t1) / 1e9
         except Exception as e:  # noqa: BLE001
             out["value_two_streams"] = repr(e)
-    # ---- after the timed region: overlapped streams, host boundary, secondary workloads, the reference (rank 0 of a 1-GPU run only)
-    if rank == 0 and world == 1 and is_main:
+    # ---- after the timed region (--full only): overlapped streams, host boundary, secondary workloads, the reference (rank 0 of a 1-GPU run only)
+    if rank == 0 and world == 1 and is_main and args.full:
         # The timed region runs big bins back to back on ONE stream, so that a k_onesweep launch has the GPU to itself and its
         # duration means something (HIP events and rocprofv3 agree). Two bins in flight fill each other's tails and gaps:
         try:

@@ -11,6 +11,7 @@
  * bin = mix(signature) % n_bins. Output is independent of the number of threads.
  */
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -38,61 +39,67 @@ struct Rng { /* counter-based: stream (seed, read) is independent of scheduling 
 constexpr uint64_t READS_PER_CHUNK = 1 << 15;
 constexpr uint32_t PACK_SUPERKMERS = 4096; /* kb_collector.h:46 */
 
-/* Two passes over the reads of a chunk, no per-chunk buffers (the first version kept a vector per (chunk, bin): 3 M vectors and
- * 60 GB of allocator traffic for the 30 Gbp workload, which scaled to 256 threads very badly): pass 1 COUNTS what every
- * (chunk, bin) cell will hold, the cells' offsets inside the final images follow from prefix sums, pass 2 regenerates the
- * reads (they are a pure function of (seed, read)) and WRITES the super-k-mers in place. */
-struct Cell {
-	uint64_t bytes = 0, n_rec = 0;
-	uint32_t n_super = 0;
-};
-
-struct CountSink {
-	Cell *cells; /* [n_bins] of this chunk */
-	void put(uint32_t bin, const uint8_t *, uint32_t n, uint32_t k)
-	{
-		Cell &c = cells[bin];
-		c.bytes += 1 + (n + 3) / 4;
-		c.n_rec += n - k + 1;
-		++c.n_super;
-	}
-};
-
-struct Cursor {
-	uint8_t *p = nullptr;
-	uint64_t *pk = nullptr;
+/* One pass over the reads (the first version kept a vector per (chunk, bin): 3 M vectors and 60 GB of allocator traffic for the 30 Gbp workload; the
+ * second generated every read twice, once to count what each (chunk, bin) cell holds and once to write it in place): every thread generates a
+ * contiguous range of chunks into blocks of its own per bin, and the images are the threads' blocks concatenated in thread order. */
+/* A thread's share of one bin in the one-pass generator: its super-k-mers in chunk order, in blocks of STAGE_BLOCK bytes, and its pack lengths
+ * (every chunk closes its own packs) */
+constexpr size_t STAGE_BLOCK = 1 << 20;
+struct Stage {
+	std::vector<std::pair<uint8_t *, size_t>> blocks;
+	std::vector<uint64_t> packs;
+	uint64_t bytes = 0, n_rec = 0, n_super = 0;
 	uint64_t cur_pack_bytes = 0;
 	uint32_t cur_pack_sk = 0;
 };
 
-struct WriteSink {
-	Cursor *cur; /* [n_bins], positioned at this chunk's cells */
+struct StageSink {
+	Stage *st; /* [n_bins] of this thread */
+	bool ok = true;
 	void put(uint32_t bin, const uint8_t *sym, uint32_t n, uint32_t k)
 	{
-		Cursor &c = cur[bin];
-		if (c.cur_pack_sk >= PACK_SUPERKMERS) {
-			*c.pk++ = c.cur_pack_bytes;
-			c.cur_pack_bytes = 0;
-			c.cur_pack_sk = 0;
+		Stage &s = st[bin];
+		if (s.cur_pack_sk >= PACK_SUPERKMERS) {
+			s.packs.push_back(s.cur_pack_bytes);
+			s.cur_pack_bytes = 0;
+			s.cur_pack_sk = 0;
 		}
 		const uint32_t nb = 1 + (n + 3) / 4;
-		uint8_t *p = c.p;
+		if (s.blocks.empty() || s.blocks.back().second + nb > STAGE_BLOCK) {
+			/* mmap'ed, not malloc'ed: the blocks go back to the system when the images are assembled, not into an allocator arena */
+			void *m = mmap(nullptr, STAGE_BLOCK, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+			uint8_t *blk = m == MAP_FAILED ? nullptr : (uint8_t *)m;
+			if (!blk) {
+				ok = false;
+				return;
+			}
+			s.blocks.emplace_back(blk, 0);
+		}
+		uint8_t *p = s.blocks.back().first + s.blocks.back().second;
 		p[0] = (uint8_t)(n - k);
-		for (uint32_t i = 1; i < nb; ++i)
-			p[i] = 0;
-		for (uint32_t i = 0; i < n; ++i)
-			p[1 + (i >> 2)] |= (uint8_t)(sym[i] << (6 - 2 * (i & 3)));
-		c.p += nb;
-		c.cur_pack_bytes += nb;
-		++c.cur_pack_sk;
+		uint32_t i = 0;
+		for (; i + 4 <= n; i += 4)
+			p[1 + (i >> 2)] = (uint8_t)(sym[i] << 6 | sym[i + 1] << 4 | sym[i + 2] << 2 | sym[i + 3]);
+		if (i < n) {
+			uint8_t last = 0;
+			for (uint32_t j = i; j < n; ++j)
+				last |= (uint8_t)(sym[j] << (6 - 2 * (j & 3)));
+			p[1 + (i >> 2)] = last;
+		}
+		s.blocks.back().second += nb;
+		s.bytes += nb;
+		s.n_rec += n - k + 1;
+		++s.n_super;
+		s.cur_pack_bytes += nb;
+		++s.cur_pack_sk;
 	}
 	void close_packs(uint32_t n_bins)
 	{
 		for (uint32_t b = 0; b < n_bins; ++b)
-			if (cur[b].cur_pack_bytes) { /* every chunk closes its own packs */
-				*cur[b].pk++ = cur[b].cur_pack_bytes;
-				cur[b].cur_pack_bytes = 0;
-				cur[b].cur_pack_sk = 0;
+			if (st[b].cur_pack_bytes) {
+				st[b].packs.push_back(st[b].cur_pack_bytes);
+				st[b].cur_pack_bytes = 0;
+				st[b].cur_pack_sk = 0;
 			}
 	}
 };
@@ -179,7 +186,7 @@ void gen_chunk(uint64_t seed, const std::vector<uint8_t> &genome, uint64_t r0, u
 	std::vector<uint32_t> mm(L), mn(L);
 	const uint32_t n_mm = L - m + 1, n_k = L - k + 1, w = k - m + 1;
 	const uint32_t mmask = (m < 16) ? ((1u << (2 * m)) - 1) : 0xFFFFFFFFu;
-	std::vector<uint32_t> dq(L);
+	std::vector<uint32_t> pre(L), suf(L);
 	for (uint64_t r = r0; r < r1; ++r) {
 		make_read(seed, genome, r, L, err_thr, rd);
 		/* canonical m-mers */
@@ -190,19 +197,19 @@ void gen_chunk(uint64_t seed, const std::vector<uint8_t> &genome, uint64_t r0, u
 			if (i + 1 >= m)
 				mm[i + 1 - m] = f < rc ? f : rc;
 		}
-		/* sliding-window minimum over w consecutive m-mers: leftmost smallest value */
-		uint32_t head = 0, tail = 0;
-		for (uint32_t i = 0; i < n_mm; ++i) {
-			while (tail > head && mm[dq[tail - 1]] > mm[i])
-				--tail;
-			dq[tail++] = i;
-			if (i + 1 >= w) {
-				const uint32_t kpos = i + 1 - w;
-				while (dq[head] < kpos)
-					++head;
-				mn[kpos] = mm[dq[head]];
-			}
+		/* sliding-window minimum over w consecutive m-mers (its value): block prefix / suffix minima (van Herk, Gil-Werman), no data-dependent branches.
+		 * A window [kpos, kpos + w) spans at most two blocks of w: min(suffix minimum at kpos, prefix minimum at kpos + w - 1) */
+		for (uint32_t b0 = 0; b0 < n_mm; b0 += w) {
+			const uint32_t b1 = std::min(n_mm, b0 + w);
+			pre[b0] = mm[b0];
+			for (uint32_t i = b0 + 1; i < b1; ++i)
+				pre[i] = std::min(pre[i - 1], mm[i]);
+			suf[b1 - 1] = mm[b1 - 1];
+			for (uint32_t i = b1 - 1; i > b0; --i)
+				suf[i - 1] = std::min(suf[i], mm[i - 1]);
 		}
+		for (uint32_t kpos = 0; kpos < n_k; ++kpos)
+			mn[kpos] = std::min(suf[kpos], pre[kpos + w - 1]);
 		/* cut into super-k-mers of equal signature */
 		uint32_t start = 0;
 		for (uint32_t i = 1; i <= n_k; ++i) {
@@ -259,16 +266,27 @@ void *kmc_synth_bins_range(uint64_t seed, uint64_t genome_len, uint64_t read_beg
 	const bool verbose = getenv("KMC_SYNTH_VERBOSE") != nullptr;
 	auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 	const double t0 = now();
-	/* pass 1: count */
-	std::vector<Cell> cells((size_t)n_chunks * n_bins);
-	run_threads([&](int t) {
-		for (uint64_t c = t; c < n_chunks; c += n_threads) {
-			uint64_t a, b;
-			chunk_range(c, a, b);
-			CountSink sink{cells.data() + (size_t)c * n_bins};
-			gen_chunk(seed, genome, a, b, read_len, err, k, sig_len, n_bins, sink);
-		}
-	});
+	/* one pass: thread t generates the contiguous chunk range [n_chunks * t / T, n_chunks * (t + 1) / T) into staging of its own, then every bin's
+	 * image is the concatenation, thread by thread, of what the threads staged for it */
+	const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)n_threads, n_chunks));
+	std::vector<std::vector<Stage>> stage(T, std::vector<Stage>(n_bins));
+	std::vector<char> staged_ok(T, 1);
+	{
+		std::vector<std::thread> th;
+		for (int t = 0; t < T; ++t)
+			th.emplace_back([&, t] {
+				StageSink sink{stage[t].data()};
+				for (uint64_t c = n_chunks * t / T; c < n_chunks * (t + 1) / T && sink.ok; ++c) {
+					uint64_t a, b;
+					chunk_range(c, a, b);
+					gen_chunk(seed, genome, a, b, read_len, err, k, sig_len, n_bins, sink);
+					sink.close_packs(n_bins);
+				}
+				staged_ok[t] = sink.ok;
+			});
+		for (auto &x : th)
+			x.join();
+	}
 	const double t1 = now();
 	Result *R = new Result();
 	R->image.assign(n_bins, nullptr);
@@ -277,62 +295,60 @@ void *kmc_synth_bins_range(uint64_t seed, uint64_t genome_len, uint64_t read_beg
 	R->n_rec.assign(n_bins, 0);
 	R->n_super.assign(n_bins, 0);
 	R->n_packs.assign(n_bins, 0);
-	/* offsets of every cell inside its bin's image / pack list (exclusive prefix over chunks), kept in the cells */
-	std::vector<uint64_t> pack_off((size_t)n_chunks * n_bins);
-	bool ok = true;
-	for (uint32_t b = 0; b < n_bins; ++b) {
-		uint64_t sz = 0, np = 0;
-		for (uint64_t c = 0; c < n_chunks; ++c) {
-			Cell &cl = cells[(size_t)c * n_bins + b];
-			const uint64_t bytes = cl.bytes;
-			R->n_rec[b] += cl.n_rec;
-			R->n_super[b] += cl.n_super;
-			cl.bytes = sz; /* now: byte offset of the cell */
-			pack_off[(size_t)c * n_bins + b] = np;
-			sz += bytes;
-			np += (cl.n_super + PACK_SUPERKMERS - 1) / PACK_SUPERKMERS;
+	std::atomic<bool> ok{std::all_of(staged_ok.begin(), staged_ok.end(), [](char x) { return x != 0; })};
+	run_threads([&](int t) {
+		for (uint32_t b = (uint32_t)t; b < n_bins; b += (uint32_t)n_threads) {
+			uint64_t sz = 0, np = 0;
+			for (int s = 0; s < T; ++s) {
+				const Stage &st = stage[s][b];
+				sz += st.bytes;
+				np += st.packs.size();
+				R->n_rec[b] += st.n_rec;
+				R->n_super[b] += st.n_super;
+			}
+			R->size[b] = sz;
+			R->n_packs[b] = np;
+			const size_t want = sz + 256;
+			if (want >= (8u << 20)) { /* big images: 2 MiB-aligned and advised huge, 256 threads first-touching 4 KiB pages do not scale */
+				const size_t al = 2u << 20, rounded = (want + al - 1) / al * al;
+				R->image[b] = (uint8_t *)aligned_alloc(al, rounded);
+				if (R->image[b])
+					(void)madvise(R->image[b], rounded, MADV_HUGEPAGE);
+			} else
+				R->image[b] = (uint8_t *)malloc(want);
+			R->packs[b] = (uint64_t *)malloc((np + 1) * 8);
+			const bool here = ok && R->image[b] && R->packs[b];
+			if (!here)
+				ok = false;
+			uint8_t *p = here ? R->image[b] : nullptr;
+			uint64_t *pk = here ? R->packs[b] : nullptr;
+			for (int s = 0; s < T; ++s) {
+				Stage &st = stage[s][b];
+				for (auto &bl : st.blocks) {
+					if (p) {
+						memcpy(p, bl.first, bl.second);
+						p += bl.second;
+					}
+					munmap(bl.first, STAGE_BLOCK);
+				}
+				st.blocks.clear();
+				if (pk && !st.packs.empty()) {
+					memcpy(pk, st.packs.data(), st.packs.size() * 8);
+					pk += st.packs.size();
+				}
+				std::vector<uint64_t>().swap(st.packs);
+			}
+			if (p)
+				memset(p, 0, 256);
 		}
-		R->size[b] = sz;
-		R->n_packs[b] = np;
-		const size_t want = sz + 256;
-		if (want >= (8u << 20)) { /* big images: 2 MiB-aligned and advised huge, 256 threads first-touching 4 KiB pages do not scale */
-			const size_t al = 2u << 20, rounded = (want + al - 1) / al * al;
-			R->image[b] = (uint8_t *)aligned_alloc(al, rounded);
-			if (R->image[b])
-				(void)madvise(R->image[b], rounded, MADV_HUGEPAGE);
-		} else
-			R->image[b] = (uint8_t *)malloc(want);
-		R->packs[b] = (uint64_t *)malloc((np + 1) * 8);
-		if (!R->image[b] || !R->packs[b])
-			ok = false;
-		else
-			memset(R->image[b] + sz, 0, 256);
-	}
+	});
 	if (!ok) {
 		kmc_synth_free(R);
 		return nullptr;
 	}
-	/* pass 2: write in place */
-	const double t2 = now();
-	run_threads([&](int t) {
-		std::vector<Cursor> cur(n_bins);
-		for (uint64_t c = t; c < n_chunks; c += n_threads) {
-			uint64_t a, b;
-			chunk_range(c, a, b);
-			for (uint32_t bi = 0; bi < n_bins; ++bi) {
-				cur[bi].p = R->image[bi] + cells[(size_t)c * n_bins + bi].bytes;
-				cur[bi].pk = R->packs[bi] + pack_off[(size_t)c * n_bins + bi];
-				cur[bi].cur_pack_bytes = 0;
-				cur[bi].cur_pack_sk = 0;
-			}
-			WriteSink sink{cur.data()};
-			gen_chunk(seed, genome, a, b, read_len, err, k, sig_len, n_bins, sink);
-			sink.close_packs(n_bins);
-		}
-	});
 	if (verbose)
-		fprintf(stderr, "[kmc_synth] %d threads, %llu reads, %u bins: count %.2f s, allocate %.2f s, write %.2f s\n", n_threads,
-		        (unsigned long long)n_reads, n_bins, t1 - t0, t2 - t1, now() - t2);
+		fprintf(stderr, "[kmc_synth] %d threads, %llu reads, %u bins: generate %.2f s, assemble %.2f s\n", T, (unsigned long long)n_reads, n_bins, t1 - t0,
+		        now() - t1);
 	*out_images = R->image.data();
 	*out_sizes = R->size.data();
 	*out_n_rec = R->n_rec.data();

@@ -165,7 +165,7 @@ def test_bench_multi_rank_body_rehearsed_over_gloo_on_the_emulated_library(tmp_p
     lib = emu.build_hostlib("small")
     base = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env = dict(base, KMC_HIP_LIB=lib, KMC_BENCH_REHEARSAL="1")
-    args = ["--reads", "3000", "--genome", "30000", "--bins", "8", "--steps", "1", "--warmup", "0", "--no-secondary", "--no-cpu-baseline", "--no-host-boundary",
+    args = ["--reads", "3000", "--genome", "30000", "--bins", "8", "--steps", "1", "--warmup", "0", "--full", "--no-secondary", "--no-cpu-baseline", "--no-host-boundary",
             "--no-two-streams", "--no-oracle-check"]
     out = {}
     for n in (1, 2, 4, 8):
@@ -195,3 +195,44 @@ def test_bench_multi_rank_body_rehearsed_over_gloo_on_the_emulated_library(tmp_p
         r = subprocess.run([sys.executable, bench, "--gpus", "1", *args], capture_output=True, text=True, timeout=300,
                            env=dict(base, KMC_BENCH_REHEARSAL="1", KMC_HIP_LIB=capi._build.LIB_HIP), cwd=str(tmp_path))
         assert r.returncode != 0 and "test builds of the library only" in (r.stdout + r.stderr)
+
+
+def test_bench_plain_run_and_dump_outputs_on_the_emulated_library(tmp_path):
+    """A plain `bench.py --gpus 1` (no --full) measures the headline figure only: the line has the contract's keys and no digest or oracle verdict. --dump-outputs
+    writes what the last timed step computed as float32 / float64 .npy files below 64 MB, equal from run to run for equal arguments, and consistent with the line."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    import emu
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bench = os.path.join(root, "bench.py")
+    base = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env = dict(base, KMC_HIP_LIB=emu.build_hostlib("small"), KMC_BENCH_REHEARSAL="1")
+    lines, dumps = [], []
+    for run in range(2):
+        d = tmp_path / ("dump%d" % run)
+        r = subprocess.run([sys.executable, bench, "--gpus", "1", "--reads", "3000", "--genome", "30000", "--bins", "8", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
+        assert r.returncode == 0, (r.stdout + r.stderr)[-1500:]
+        line = json.loads(r.stdout.rstrip("\n").splitlines()[-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "tallies"):
+            assert key in line, key
+        assert line["steps"] == 2 and line["warmup"] == 1
+        assert line["self_check"]["output_digest"] is None and line["self_check"]["oracle_bins_equal"] is None and "secondary" not in line
+        files = sorted(os.listdir(d))
+        assert files == ["bin_ids.npy", "bin_stats.npy", "lut_sample.npy", "records_sample.npy", "tallies.npy"], files
+        arrs = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) < 64 << 20
+        lines.append(line)
+        dumps.append(arrs)
+    t = lines[0]["tallies"]
+    assert list(dumps[0]["tallies.npy"]) == [t["n_unique"], t["n_cutoff_min"], t["n_cutoff_max"], t["n_total"]]
+    assert dumps[0]["bin_stats.npy"][:, :4].sum(axis=0).tolist() == list(dumps[0]["tallies.npy"])
+    assert (dumps[0]["records_sample.npy"] >= 0).any()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
