@@ -313,20 +313,27 @@ void kmc_hip_split_reads_free(kmc_hip_ctx *ctx, kmc_hip_s1_plan *plan);
  * overlap by k - 1 symbols): an optional title, then symbols only (CSplitter::GetSeqLongRead, splitter.cpp:70-86). Lines of mem_part_pmm_reads
  * symbols or more inside an ordinary part, and long-read parts, reach the reference's super-k-mer loop in pieces that overlap by k - 1 symbols
  * (splitter.cpp:141-145, :226-231, :80-84); the kernels cut super-k-mers at the same piece starts, so the three sums agree with the reference's.
+ * file_type 2 = a multi-line FASTA part as CFastqReader::GetPartFromMultilneFasta cuts it (ReadType::na, fastq_reader.cpp:399-468: a title keeps its
+ * run of end-of-line bytes, the sequence text has none, a part may start inside a sequence); it is split as CSplitter::GetSeq's MULTILINE_FASTA branch
+ * does (splitter.cpp:304-323), *n_reads = titles in the part, and part_kind must be 0.
  * Returns 0, a negative KMC_HIP_E* code, or KMC_HIP_UNCOVERED: the text is MALFORMED in a way CSplitter::GetSeq tolerates and the kernels do not
- * reproduce (blank lines, quality of another length than its sequence, a lone '\r', control characters) — nothing was produced; the stage-1 worker
+ * reproduce (blank lines, quality of another length than its sequence, a lone '\r', control characters; multi-line FASTA: a part that ends inside a
+ * title line) — nothing was produced; the stage-1 worker
  * stops the run with an error (it has no path into the reference splitter unless built with -DKMC_HIP_S1_REFERENCE_FALLBACK). Calls on one
  * (dev, slot) are serialised. */
 #define KMC_HIP_UNCOVERED 1
 typedef struct kmc_hip_split_params {
 	uint32_t kmer_len, signature_len, n_bins, max_x; /* max_x: CKMCParams::max_x (0..3) */
 	uint32_t both_strands;
-	uint32_t file_type;                              /* 0 = FASTA (one line per sequence), 1 = FASTQ */
+	uint32_t file_type;                              /* 0 = FASTA (one line per sequence), 1 = FASTQ, 2 = multi-line FASTA (-fm) */
 	uint64_t line_cap;                               /* CKMCParams::mem_part_pmm_reads */
 	uint32_t part_kind;                              /* 0 = whole records (ReadType::normal_read), 1 = ReadType::long_read */
 	uint32_t reserved;                               /* 0 */
 } kmc_hip_split_params;
 int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, uint32_t signature_len);
+/* 1 if kmc_hip_split_part takes parts of this file_type, else 0. Added without a new ABI version: a loader that finds no such symbol takes file_type 0
+ * and 1 only. */
+int kmc_hip_split_covers(uint32_t file_type);
 int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint8_t *recs,
                        uint64_t recs_capacity, uint64_t *recs_bytes, uint64_t *bin_off, uint64_t *bin_bytes, uint64_t *bin_kmers, uint64_t *bin_superkmers, uint64_t *bin_plus_x,
                        uint64_t *n_reads);

@@ -88,7 +88,7 @@ SYMBOLS = [
     "kmc_hip_host_register", "kmc_hip_host_unregister", "kmc_hip_host_alloc", "kmc_hip_host_free", "kmc_hip_synchronize",
     "kmc_hip_debug_expand", "kmc_hip_debug_compact", "kmc_hip_debug_split_reads",
     "kmc_hip_split_reads_plan", "kmc_hip_split_reads_emit", "kmc_hip_split_reads_free",
-    "kmc_hip_split_set_map", "kmc_hip_split_part",
+    "kmc_hip_split_set_map", "kmc_hip_split_part", "kmc_hip_split_covers",
 ]
 
 _LIB = None
@@ -167,6 +167,8 @@ def load():
     L.kmc_hip_debug_expand.argtypes = [vp, C.c_int, C.POINTER(BinParams), vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp]
     L.kmc_hip_debug_compact.argtypes = [vp, C.c_int, C.POINTER(BinParams), vp, C.c_uint64, vp, C.c_uint64, u64p, vp, u64p]
     L.kmc_hip_debug_split_reads.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, u64p]
+    if hasattr(L, "kmc_hip_split_covers"):  # added within ABI version 4: a library without it takes file_type 0 and 1 only
+        L.kmc_hip_split_covers.argtypes = [C.c_uint32]
     _LIB = L
     return L
 

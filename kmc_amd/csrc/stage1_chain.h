@@ -31,6 +31,8 @@ struct S1PartParams {
 	const int *d_sig_to_bin;                                  /* device: 4^m + 1 entries */
 	u64 sk_guess_div = 8;                                     /* first guess of the number of super-k-mers: symbols / this + 4096 */
 	bool sorted_emit = false;                                 /* records through a sort by bin (k_s1_emit_sorted) instead of k_s1_emit: bins in read order */
+	bool multiline_fasta = false;                             /* a multi-line FASTA part (ReadType::na, GetSeq splitter.cpp:304-323): k_s1_ml_text_to_codes;
+	                                                           * lines_per_record is not used */
 };
 struct S1PartResult {
 	const uint8_t *d_recs = nullptr; /* device: bin b's records at d_recs + bin_off[b], bin_bytes[b] of them */
@@ -76,33 +78,62 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 	if (P.line_cap < (u64)P.k + S1_WG_TILE + 2)
 		return S1_CHAIN_UNCOVERED;
 	const u64 stride = P.line_cap - P.k + 1;
-	/* ---- text -> codes. A line of real reads is tens of bytes; text with more line ends than size / 4 is not taken. */
-	const u64 nl_cap = lpr ? size / 4 + 1024 : 1;
-	const u32 tiles = (u32)((size + S1_TXT_TILE - 1) / S1_TXT_TILE);
-	int8_t *d_codes = (int8_t *)be.alloc(size + 16);
-	u64 *d_nl = (u64 *)be.alloc(nl_cap * 8);
-	u64 *d_seq_start = (u64 *)be.alloc_uninit((nl_cap / (lpr ? lpr : 1) + 2) * 8);
-	u64 *d_status = (u64 *)be.alloc((size_t)tiles * 16);
-	S1_LAUNCH(B, be, k_s1_text_to_codes, dim3(tiles), dim3(S1_BLOCK), d_text, size, lpr, d_status, d_status + tiles, d_ticket, d_codes, d_nl, nl_cap, d_seq_start, d_small,
-	          d_err);
-	if (!be.d2h(small, d_small, sizeof small))
-		return S1_CHAIN_BACKEND_FAILURE;
-	u32 err = (u32)(small[3] >> 32);
-	if (err & (S1_TEXT_BAD | KERR_CAPACITY))
-		return S1_CHAIN_UNCOVERED;
-	if (err) {
-		R.device_error = err;
-		return S1_CHAIN_DEVICE_ERROR;
+	u64 n;
+	int8_t *d_codes;
+	u32 err;
+	if (P.multiline_fasta) {
+		/* ---- text -> codes, multi-line FASTA: per-sequence arrays sized by titles (two bytes each at least), not by lines */
+		const u64 seq_cap = size / 2 + 2;
+		const u32 tiles = (u32)((size + S1_TXT_TILE - 1) / S1_TXT_TILE);
+		d_codes = (int8_t *)be.alloc(size + 16);
+		u64 *d_seq_start = (u64 *)be.alloc_uninit(seq_cap * 8);
+		u64 *d_status = (u64 *)be.alloc((size_t)tiles * 24);
+		S1_LAUNCH(B, be, k_s1_ml_text_to_codes, dim3(tiles), dim3(S1_BLOCK), d_text, size, d_status, d_status + tiles, d_status + 2 * (size_t)tiles, d_ticket, d_codes,
+		          d_seq_start, seq_cap, d_small, d_err);
+		if (!be.d2h(small, d_small, sizeof small))
+			return S1_CHAIN_BACKEND_FAILURE;
+		err = (u32)(small[3] >> 32);
+		if (err & (S1_TEXT_BAD | KERR_CAPACITY))
+			return S1_CHAIN_UNCOVERED;
+		if (err) {
+			R.device_error = err;
+			return S1_CHAIN_DEVICE_ERROR;
+		}
+		n = small[1];
+		R.n_symbols = n;
+		R.n_reads = small[0];
+		S1_LAUNCH(B, be, k_s1_ml_marks, dim3((u32)((small[0] + 1 + 255) / 256)), dim3(256), d_text, n, (const u64 *)d_seq_start, small[0], P.line_cap, stride, d_codes,
+		          d_has_marks);
+	} else {
+		/* ---- text -> codes. A line of real reads is tens of bytes; text with more line ends than size / 4 is not taken. */
+		const u64 nl_cap = lpr ? size / 4 + 1024 : 1;
+		const u32 tiles = (u32)((size + S1_TXT_TILE - 1) / S1_TXT_TILE);
+		d_codes = (int8_t *)be.alloc(size + 16);
+		u64 *d_nl = (u64 *)be.alloc(nl_cap * 8);
+		u64 *d_seq_start = (u64 *)be.alloc_uninit((nl_cap / (lpr ? lpr : 1) + 2) * 8);
+		u64 *d_status = (u64 *)be.alloc((size_t)tiles * 16);
+		S1_LAUNCH(B, be, k_s1_text_to_codes, dim3(tiles), dim3(S1_BLOCK), d_text, size, lpr, d_status, d_status + tiles, d_ticket, d_codes, d_nl, nl_cap, d_seq_start, d_small,
+		          d_err);
+		if (!be.d2h(small, d_small, sizeof small))
+			return S1_CHAIN_BACKEND_FAILURE;
+		err = (u32)(small[3] >> 32);
+		if (err & (S1_TEXT_BAD | KERR_CAPACITY))
+			return S1_CHAIN_UNCOVERED;
+		if (err) {
+			R.device_error = err;
+			return S1_CHAIN_DEVICE_ERROR;
+		}
+		const u64 n_lines = small[0];
+		n = small[1];
+		R.n_symbols = n;
+		if (lpr) {
+			const u64 lines = n_lines + (text_ends_with_newline ? 0 : 1); /* titles in the part: every lpr-th line, an unterminated last line included */
+			R.n_reads = (lines + lpr - 1) / lpr;
+			S1_LAUNCH(B, be, k_s1_check_records, dim3((u32)((n_lines / lpr + 1 + 255) / 256)), dim3(256), d_text, size, (const u64 *)d_nl, n_lines, lpr, P.line_cap, stride,
+			          (const u64 *)d_seq_start, d_codes, d_has_marks, d_err);
+		} else if (n > stride) /* n_reads of a long-read part: the caller knows whether it took a title off */
+			S1_LAUNCH(B, be, k_s1_mark_raw, dim3(1), dim3(256), d_codes, n, stride, d_has_marks);
 	}
-	const u64 n_lines = small[0], n = small[1];
-	R.n_symbols = n;
-	if (lpr) {
-		const u64 lines = n_lines + (text_ends_with_newline ? 0 : 1); /* titles in the part: every lpr-th line, an unterminated last line included */
-		R.n_reads = (lines + lpr - 1) / lpr;
-		S1_LAUNCH(B, be, k_s1_check_records, dim3((u32)((n_lines / lpr + 1 + 255) / 256)), dim3(256), d_text, size, (const u64 *)d_nl, n_lines, lpr, P.line_cap, stride,
-		          (const u64 *)d_seq_start, d_codes, d_has_marks, d_err);
-	} else if (n > stride) /* n_reads of a long-read part: the caller knows whether it took a title off */
-		S1_LAUNCH(B, be, k_s1_mark_raw, dim3(1), dim3(256), d_codes, n, stride, d_has_marks);
 	/* ---- codes -> super-k-mers. Their number is only known afterwards: a guess, and a second cut with the exact number when it was short. */
 	u64 n_sk = 0, cap = n / P.sk_guess_div + 4096;
 	u64 *d_pos = nullptr;

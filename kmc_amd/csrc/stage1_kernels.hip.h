@@ -719,6 +719,166 @@ __global__ void __launch_bounds__(256) k_s1_check_records(const uint8_t *__restr
 	}
 }
 
+/* ------------------------------------------------------------------------------------------------ multi-line FASTA (-fm)
+ * What reaches the splitter from CFastqReader::GetPartFromMultilneFasta (fastq_reader.cpp:399-468, ReadType::na :579-583) is simpler than single-line
+ * FASTA: a title keeps its whole run of end-of-line bytes (SkipNextEOL :917-929), every other '\n' / '\r' is gone, and a part starts at a title or,
+ * when the previous part held one sequence only, inside a sequence (its last k - 1 symbols carried over). CSplitter::GetSeq, branch MULTILINE_FASTA
+ * (splitter.cpp:304-323), walks it with three states, written here for any text:
+ *   SEQ       '>' starts a title (one read counted) -> TITLE; any other byte is a symbol (an end of line too: a negative code)
+ *   TITLE     up to and including the first '\n' / '\r' every byte is the title's: that end of line -> TITLE_EOL
+ *   TITLE_EOL an end of line is dropped (-> SEQ); '>' starts a title; any other byte is a symbol (-> SEQ)
+ * The state in front of a byte is data-parallel: it is TITLE exactly when the last '>' or end of line before the byte is a '>' (a title runs from its
+ * '>' to its first end of line, and a '>' inside it changes nothing). TITLE_EOL and SEQ differ only on an end of line, and both go to the same state
+ * after any byte, so the state in front of byte p0 follows from "TITLE or not" in front of byte p0 - 1 and byte p0 - 1 itself. That is why a thread's
+ * share of the latest-event scan is bytes p0 - 1 .. p0 + 14, one byte behind the bytes it classifies: the exclusive scan then answers for p0 - 1. */
+enum : u32 { S1_ML_SEQ = 0, S1_ML_TITLE = 1, S1_ML_TITLE_EOL = 2 };
+
+/* k_s1_ml_text_to_codes: one multi-line FASTA part -> the code stream of the kernels above. A title (its '>', the text, its first end of line and one more
+ * end of line right behind it) becomes ONE negative separator: the '>' is kept and s1_symbol_code gives it -1. seq_start[i] = where sequence i starts in the
+ * code stream (sequence 0 starts at 0 when the part starts inside a sequence, the others behind their separator), seq_cap entries (a title takes two bytes
+ * at least: size / 2 + 2 suffice). totals[0] = titles (CSplitter::n_reads), totals[1] = bytes of the code stream. A part that ends inside a title line
+ * (GetSeq would read past the part) raises S1_TEXT_BAD. Three decoupled look-backs per tile: the latest event (lookback64_last over (position + 1) << 1 |
+ * is '>'), then kept bytes and titles (two sums, one wave each). status: 3 zeroed u64 per tile. */
+__global__ void __launch_bounds__(S1_BLOCK) k_s1_ml_text_to_codes(const uint8_t *__restrict__ text, u64 n, u64 *status_ev, u64 *status_keep, u64 *status_titles,
+                                                                   u32 *ticket_ctr, int8_t *__restrict__ codes, u64 *__restrict__ seq_start, u64 seq_cap, u64 *totals,
+                                                                   u32 *err)
+{
+	__shared__ u64 s_tmp64[S1_BLOCK / 64 + 1];
+	__shared__ u32 s_tmp[S1_BLOCK / 64 + 1];
+	__shared__ u64 s_carry_ev, s_carry_keep, s_carry_titles;
+	__shared__ u32 s_ticket;
+	const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	if (tid == 0)
+		s_ticket = atomicAdd(ticket_ctr, 1u);
+	__syncthreads();
+	const u32 tile = s_ticket;
+	const u32 num_tiles = (u32)((n + S1_TXT_TILE - 1) / S1_TXT_TILE);
+	if (tile >= num_tiles)
+		return;
+	const u64 p0 = (u64)tile * S1_TXT_TILE + (u64)tid * S1_TXT_PER;
+	uint8_t c[S1_TXT_PER];
+	static_assert(S1_TXT_PER == 16, "one 16-byte load per thread");
+	if (p0 + S1_TXT_PER <= n) {
+		u32 w[4];
+		__builtin_memcpy(w, text + p0, 16);
+#pragma unroll
+		for (int j = 0; j < S1_TXT_PER; ++j)
+			c[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
+	} else {
+#pragma unroll
+		for (int j = 0; j < S1_TXT_PER; ++j)
+			c[j] = p0 + j < n ? text[p0 + j] : (uint8_t)0;
+	}
+	const uint8_t cb = p0 < n && p0 > 0 ? text[p0 - 1] : (uint8_t)0; /* the byte in front: the last one of the thread before */
+	auto is_eol = [](uint8_t x) { return x == '\n' || x == '\r'; };
+	/* ---- the latest '>' or end of line among bytes p0 - 1 .. p0 + 14 */
+	u64 ev = 0;
+	if (p0 > 0 && p0 < n && (cb == '>' || is_eol(cb)))
+		ev = (p0 << 1) | (cb == '>' ? 1u : 0u); /* (position + 1) << 1 of byte p0 - 1 */
+#pragma unroll
+	for (int j = 0; j < S1_TXT_PER - 1; ++j)
+		if (p0 + j < n && (c[j] == '>' || is_eol(c[j])))
+			ev = ((p0 + j + 1) << 1) | (c[j] == '>' ? 1u : 0u);
+	const u64 ev_before = block_excl_max<S1_BLOCK / 64, u64>(ev, s_tmp64);
+	const u64 ev_incl = wave_incl_max<u64>(ev, lane);
+	if (lane == 63)
+		s_tmp64[wave] = ev_incl;
+	__syncthreads();
+	if (wave == 0) {
+		u64 tile_ev = 0;
+#pragma unroll
+		for (int i = 0; i < S1_BLOCK / 64; ++i)
+			tile_ev = s_tmp64[i] > tile_ev ? s_tmp64[i] : tile_ev;
+		const u64 carry = lookback64_last(status_ev, tile, tile_ev, lane, err);
+		if (lane == 0)
+			s_carry_ev = carry;
+	}
+	__syncthreads();
+	const u64 last_ev = ev_before ? ev_before : s_carry_ev; /* in front of byte p0 - 1 (tiles before this one hold only earlier positions) */
+	u32 st = (last_ev & 1u) ? S1_ML_TITLE : S1_ML_SEQ;
+	if (p0 > 0 && p0 < n) /* byte p0 - 1 moves the state: TITLE_EOL and SEQ go the same way on every byte */
+		st = cb == '>' ? S1_ML_TITLE : (st == S1_ML_TITLE ? (is_eol(cb) ? S1_ML_TITLE_EOL : S1_ML_TITLE) : S1_ML_SEQ);
+	/* ---- the bytes of this thread: kept (code stream) and title starts */
+	u32 keep = 0, title = 0, n_keep = 0, n_title = 0;
+#pragma unroll
+	for (int j = 0; j < S1_TXT_PER; ++j) {
+		if (p0 + j >= n)
+			break;
+		const uint8_t x = c[j];
+		if (st == S1_ML_TITLE) {
+			if (is_eol(x))
+				st = S1_ML_TITLE_EOL;
+		} else if (x == '>') {
+			keep |= 1u << j;
+			title |= 1u << j;
+			++n_keep, ++n_title;
+			st = S1_ML_TITLE;
+		} else if (st == S1_ML_TITLE_EOL && is_eol(x))
+			st = S1_ML_SEQ;
+		else {
+			keep |= 1u << j;
+			++n_keep;
+			st = S1_ML_SEQ;
+		}
+		if (p0 + j == n - 1 && st == S1_ML_TITLE)
+			atomicOr(err, S1_TEXT_BAD); /* the part ends inside a title line */
+	}
+	u32 tile_packed; /* at most S1_TXT_TILE of each per tile: 16 bits apiece */
+	const u32 before_packed = block_excl_sum<S1_BLOCK / 64, u32>(n_keep | (n_title << 16), s_tmp, tile_packed);
+	if (wave < 2) {
+		const u64 agg = wave == 0 ? (u64)(tile_packed & 0xFFFFu) : (u64)(tile_packed >> 16);
+		const u64 excl = lookback64(wave == 0 ? status_keep : status_titles, tile, agg, lane, err, KERR_WATCHDOG | KERR_AT_STAGE1);
+		if (lane == 0) {
+			(wave == 0 ? s_carry_keep : s_carry_titles) = excl;
+			if (tile == num_tiles - 1)
+				totals[wave == 0 ? 1 : 0] = excl + agg;
+		}
+	}
+	__syncthreads();
+	u64 at = s_carry_keep + (before_packed & 0xFFFFu);
+	/* sequence numbers: titles before this one, + 1 when the part starts inside a sequence (which is sequence 0) */
+	u64 seq = s_carry_titles + (before_packed >> 16) + (text[0] != '>' ? 1u : 0u);
+	if (p0 == 0 && text[0] != '>')
+		seq_start[0] = 0;
+#pragma unroll
+	for (int j = 0; j < S1_TXT_PER; ++j) {
+		if (!(keep & (1u << j)))
+			continue;
+		codes[at] = s1_symbol_code(c[j]);
+		++at;
+		if (title & (1u << j)) {
+			if (seq < seq_cap)
+				seq_start[seq] = at; /* behind the separator */
+			else
+				atomicOr(err, KERR_CAPACITY);
+			++seq;
+		}
+	}
+}
+
+/* The piece starts (S1_PIECE_MARK) of the sequences of a multi-line part: one thread per sequence (n_titles + 1 threads at least; sequence i runs from
+ * seq_start[i] to the separator in front of seq_start[i + 1], the last one to the end of the n codes). GetSeq takes at most line_cap symbols per call and
+ * steps back k - 1 when the cap stopped it, so its pieces start at start + j * stride (stride = line_cap - k + 1), as on a long single line. It does not
+ * step back when a '>' or the end of the part is next: then the sequence has exactly (j + 1) * stride + k - 1 symbols, the last k-mer starts at
+ * (j + 1) * stride - 1, and a mark at (j + 1) * stride or beyond lies where no k-mer of this sequence starts — so marking every multiple of the stride
+ * inside a sequence of line_cap symbols or more gives the reference's piece starts at every position where a k-mer can start. */
+__global__ void __launch_bounds__(256) k_s1_ml_marks(const uint8_t *__restrict__ text, u64 n, const u64 *__restrict__ seq_start, u64 n_titles, u64 line_cap, u64 stride,
+                                                       int8_t *__restrict__ codes, u64 *has_marks)
+{
+	const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+	const u64 n_seq = n_titles + (text[0] != '>' ? 1u : 0u);
+	if (i >= n_seq)
+		return;
+	const u64 s0 = seq_start[i], e = i + 1 < n_seq ? seq_start[i + 1] - 1 : n;
+	const u64 len = e - s0;
+	if (len >= line_cap) {
+		for (u64 p = stride; p < len; p += stride)
+			if (codes[s0 + p] >= 0)
+				codes[s0 + p] |= S1_PIECE_MARK;
+		*has_marks = 1;
+	}
+}
+
 /* n_plus_x_recs per bin: how many (k+x)-mer records the reference's stage 2 expands each super-k-mer into (kb_collector.cpp:83-100,
  * kb_collector.h:72-118) — the third sum a CKmerBinCollector keeps, which stage 2 sizes its arrays with. One thread per super-k-mer walks
  * its k-mers comparing the first four symbols of the k-mer with those of its reverse complement. */

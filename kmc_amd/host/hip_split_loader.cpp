@@ -22,6 +22,7 @@ struct SplitApi {
 	int (*split_part)(kmc_hip_ctx *, int, int, const kmc_hip_split_params *, const uint8_t *, uint64_t, uint8_t *, uint64_t, uint64_t *, uint64_t *, uint64_t *,
 	                  uint64_t *, uint64_t *, uint64_t *, uint64_t *) = nullptr;
 	const char *(*last_error)(kmc_hip_ctx *) = nullptr;
+	int (*covers)(uint32_t) = nullptr; /* optional: a library without kmc_hip_split_covers takes FASTA and FASTQ only */
 	kmc_hip_ctx *ctx = nullptr;
 	int n_dev = 1, n_slots = 1;
 	std::string err;
@@ -38,6 +39,7 @@ void bind()
 	g_split.set_map = reinterpret_cast<decltype(g_split.set_map)>(dlsym(so, "kmc_hip_split_set_map"));
 	g_split.split_part = reinterpret_cast<decltype(g_split.split_part)>(dlsym(so, "kmc_hip_split_part"));
 	g_split.last_error = reinterpret_cast<decltype(g_split.last_error)>(dlsym(so, "kmc_hip_last_error"));
+	g_split.covers = reinterpret_cast<decltype(g_split.covers)>(dlsym(so, "kmc_hip_split_covers"));
 	if (!g_split.set_map || !g_split.split_part || !g_split.last_error) {
 		g_split.err = "libkmc_hip.so lacks kmc_hip_split_set_map / kmc_hip_split_part";
 		g_split.ctx = nullptr;
@@ -63,6 +65,7 @@ struct HipSplitEngine : KmcSplitEngine {
 		map_hash = h ? h : 1;
 	}
 	std::string last_error() override { return err; }
+	bool covers_multiline_fasta() const override { return g_split.ctx && g_split.covers && g_split.covers(2) == 1; }
 	int split_part(const uint8_t *text, uint64_t size, bool long_read, KmcSplitResult &out) override
 	{
 		if (!g_split.ctx) {

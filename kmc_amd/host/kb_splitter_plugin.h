@@ -21,11 +21,12 @@
  *
  * FAILS CLOSED (round 5): this worker has no path into the reference's CSplitter. What the engine does not cover stops the run through
  * CCriticalErrorHandler with a message that names it —
- *   per job : input other than FASTA / FASTQ (multi-line FASTA, BAM, KMC), homopolymer compression (-hc), histogram estimation while counting (--opt-out-size; -e alone runs the reference's estimate-only worker, not this one):
+ *   per job : input other than FASTA / FASTQ (BAM, KMC; multi-line FASTA unless the engine covers_multiline_fasta()), homopolymer compression (-hc), histogram estimation while counting (--opt-out-size; -e alone runs the reference's estimate-only worker, not this one):
  *             "use kmc_hip" (the reference's stage 1 + this library's stage 2) is the answer the message gives;
  *   per part: KMC_SPLIT_UNCOVERED — MALFORMED text that CSplitter::GetSeq happens to tolerate (blank lines, a quality string of another length than its
  *             sequence, control characters, a lone '\r').
- * Parts the reader labelled ReadType::long_read (queues.h:40) and lines of mem_part_pmm_reads symbols or more go through the engine like any other.
+ * Parts the reader labelled ReadType::long_read (queues.h:40) and lines of mem_part_pmm_reads symbols or more go through the engine like any other, and so
+ * do the ReadType::na parts of multi-line FASTA (fastq_reader.cpp:399-468, :579-583) with an engine that covers them (file_type 2).
  * Only a build with -DKMC_HIP_S1_REFERENCE_FALLBACK (no shipped binary has it; oracle/_ref/kmc_emu_s1_fb is the test build) AND $KMC_HIP_S1_FALLBACK=1
  * in the environment hands such jobs / parts to the reference (CWSplitter_ref / a CSplitter of this thread, our buffers pushed first) and says so on stderr;
  * nothing run that way is covered by this repo's parity claims.
@@ -106,12 +107,12 @@ class CWSplitter {
 	bool both_strands;
 	uint64 n_reads = 0;
 	/* KMC_HIP_VERBOSE=1: one line per worker on stderr when it finishes */
-	uint64 st_parts = 0, st_long_parts = 0, st_uncovered_parts = 0, st_pieces = 0, st_cut_pieces = 0, st_pushes = 0, st_bytes = 0;
+	uint64 st_parts = 0, st_long_parts = 0, st_ml_parts = 0, st_uncovered_parts = 0, st_pieces = 0, st_cut_pieces = 0, st_pushes = 0, st_bytes = 0;
 	long long st_engine_ns = 0;
 
-	static const char *uncovered_job(const CKMCParams &P)
+	static const char *uncovered_job(const CKMCParams &P, bool multiline_covered)
 	{
-		if (P.file_type != InputType::FASTA && P.file_type != InputType::FASTQ)
+		if (P.file_type != InputType::FASTA && P.file_type != InputType::FASTQ && !(P.file_type == InputType::MULTILINE_FASTA && multiline_covered))
 			return "an input format other than FASTA / FASTQ (multi-line FASTA, BAM, KMC)";
 		if (P.homopolymer_compressed)
 			return "homopolymer compression (-hc)";
@@ -192,6 +193,20 @@ class CWSplitter {
 		for (uint32 i = 0; i < (uint32)bins.size(); ++i)
 			push(i);
 	}
+	static KmcSplitEngine *make_engine(CKMCParams &Params, CKMCQueues &Queues)
+	{
+		KmcSplitParams sp;
+		sp.kmer_len = Params.kmer_len;
+		sp.signature_len = Params.signature_len;
+		sp.n_bins = Params.n_bins;
+		sp.max_x = Params.max_x;
+		sp.both_strands = Params.both_strands ? 1 : 0;
+		sp.file_type = Params.file_type == InputType::FASTQ ? 1 : Params.file_type == InputType::MULTILINE_FASTA ? 2 : 0;
+		sp.line_cap = (uint64_t)Params.mem_part_pmm_reads;
+		sp.sig_to_bin = Queues.s_mapper->GetMap();
+		static std::atomic<int> next_idx{0};
+		return kmc_make_split_engine(sp, next_idx++ % (int)Params.n_splitters, (int)Params.n_splitters);
+	}
 
 public:
 	CWSplitter(CKMCParams &Params, CKMCQueues &Queues)
@@ -207,13 +222,16 @@ public:
 		max_x = Params.max_x;
 		both_strands = Params.both_strands;
 		buffer_size = Params.bin_part_size;
-		if (const char *what = uncovered_job(Params)) {
+		if (Params.file_type == InputType::MULTILINE_FASTA)
+			engine.reset(make_engine(Params, Queues)); /* whether the format is covered is the engine's answer */
+		if (const char *what = uncovered_job(Params, engine && engine->covers_multiline_fasta())) {
 #ifdef KMC_HIP_S1_REFERENCE_FALLBACK
 			const char *fb = getenv("KMC_HIP_S1_FALLBACK");
 			if (fb && fb[0] == '1') {
 				static std::atomic<int> said{0};
 				if (!said++)
 					fprintf(stderr, "[kmc_hip stage 1] %s: the REFERENCE splitter runs stage 1 of this job (KMC_HIP_S1_FALLBACK=1); nothing of stage 1 is on the device\n", what);
+				engine.reset();
 				ref = std::make_unique<CWSplitter_ref>(Params, Queues);
 				return;
 			}
@@ -229,17 +247,8 @@ public:
 		}
 #endif
 		bins.resize(Params.n_bins);
-		KmcSplitParams sp;
-		sp.kmer_len = Params.kmer_len;
-		sp.signature_len = Params.signature_len;
-		sp.n_bins = Params.n_bins;
-		sp.max_x = Params.max_x;
-		sp.both_strands = Params.both_strands ? 1 : 0;
-		sp.file_type = Params.file_type == InputType::FASTQ ? 1 : 0;
-		sp.line_cap = (uint64_t)Params.mem_part_pmm_reads;
-		sp.sig_to_bin = Queues.s_mapper->GetMap();
-		static std::atomic<int> next_idx{0};
-		engine.reset(kmc_make_split_engine(sp, next_idx++ % (int)Params.n_splitters, (int)Params.n_splitters));
+		if (!engine)
+			engine.reset(make_engine(Params, Queues));
 		if (!engine)
 			CCriticalErrorHandler::Inst().HandleCriticalError("Error: no stage-1 split engine available");
 	}
@@ -260,10 +269,13 @@ public:
 			ReadType read_type;
 			if (!pq->pop(part, size, read_type))
 				continue;
-			if (read_type == ReadType::na) /* only the multi-line FASTA reader makes these (fastq_reader.cpp:253-341), and that format is refused above */
+			/* only the multi-line FASTA reader makes ReadType::na parts (fastq_reader.cpp:399-468, :579-583); the constructor took that format only
+			 * from an engine that covers it, and the engine was made with file_type 2 */
+			if (read_type == ReadType::na && params->file_type != InputType::MULTILINE_FASTA)
 				CCriticalErrorHandler::Inst().HandleCriticalError("Error: stage 1 on the device got a part of ReadType::na");
 			const bool long_read = read_type == ReadType::long_read;
 			st_long_parts += long_read ? 1 : 0;
+			st_ml_parts += read_type == ReadType::na ? 1 : 0;
 			KmcSplitResult r;
 			const auto t0 = std::chrono::steady_clock::now();
 			const int rc = engine->split_part(part, size, long_read, r);
@@ -276,6 +288,10 @@ public:
 					continue;
 				}
 #endif
+				if (read_type == ReadType::na)
+					CCriticalErrorHandler::Inst().HandleCriticalError(
+					    "Error: stage 1 on the device: a part of the multi-line FASTA input ends inside a title line (a title longer than the reader's part). "
+					    "Run this input with kmc_hip (the reference's stage 1, stage 2 on the device).");
 				CCriticalErrorHandler::Inst().HandleCriticalError(
 				    "Error: stage 1 on the device: a part of the input is malformed FASTA / FASTQ text (a blank line, a quality string of another length than its "
 				    "sequence, a control character or a lone carriage return). The device splitter does not guess what such text means; "
@@ -299,10 +315,10 @@ public:
 		KmcTimeline::mark_first_last(nullptr, "splitter: last worker done");
 		if (getenv("KMC_HIP_VERBOSE"))
 			fprintf(stderr, "[kmc_hip stage 1] worker: %llu parts through the engine (%.3f s inside; %llu of them long-read parts), %llu uncovered parts, "
-			                "%llu bin pieces (%llu cut record by record), %llu buffers / %.1f MB pushed\n",
+			                "%llu bin pieces (%llu cut record by record), %llu buffers / %.1f MB pushed, %llu multi-line FASTA parts\n",
 			        (unsigned long long)st_parts, st_engine_ns * 1e-9, (unsigned long long)st_long_parts, (unsigned long long)st_uncovered_parts,
 			        (unsigned long long)st_pieces,
-			        (unsigned long long)st_cut_pieces, (unsigned long long)st_pushes, st_bytes / 1e6);
+			        (unsigned long long)st_cut_pieces, (unsigned long long)st_pushes, st_bytes / 1e6, (unsigned long long)st_ml_parts);
 	}
 
 	void GetTotal(uint64 &_n_reads)

@@ -20,7 +20,7 @@
 struct KmcSplitParams {
 	uint32_t kmer_len, signature_len, n_bins, max_x;
 	int both_strands;
-	int file_type;             /* 0 = FASTA (one line per sequence), 1 = FASTQ */
+	int file_type;             /* 0 = FASTA (one line per sequence), 1 = FASTQ, 2 = multi-line FASTA (ReadType::na parts; only for an engine that covers_multiline_fasta()) */
 	uint64_t line_cap;         /* mem_part_pmm_reads: longer lines are cut into pieces overlapping by kmer_len - 1 symbols (splitter.cpp:141-145) */
 	const int32_t *sig_to_bin; /* CSignatureMapper's map, 4^signature_len + 1 entries (s_mapper.h:232) */
 };
@@ -43,6 +43,8 @@ struct KmcSplitEngine {
 	virtual ~KmcSplitEngine() {}
 	virtual int split_part(const uint8_t *text, uint64_t size, bool long_read, KmcSplitResult &out) = 0;
 	virtual std::string last_error() = 0;
+	/* parts of multi-line FASTA (file_type 2: CFastqReader::GetPartFromMultilneFasta, split as CSplitter::GetSeq's MULTILINE_FASTA branch) */
+	virtual bool covers_multiline_fasta() const { return false; }
 };
 
 /* Provided by exactly one engine implementation linked into the binary. */

@@ -67,6 +67,57 @@ def make_fastq(path: str, seed: int, genome_len: int, n_reads: int, read_len: in
     return write_fastq(path, make_reads(seed, genome_len, n_reads, read_len, err))
 
 
+def make_multiline_fasta(path: str, seed: int, contig_lens, line_width: int = 60, lower_frac: float = 0.0, n_run_per_mbp: float = 0.0,
+                         n_run_len: int = 200, n_empty: int = 0, eol: bytes = b"\n") -> int:
+    """Write an assembly-like multi-line FASTA (the input of -fm): one record per contig length in `contig_lens`, sequence wrapped at
+    `line_width` columns, every line ended by `eol` (b"\n" or b"\r\n"). Sequence = i.i.d. uniform ACGT; a share `lower_frac` of it is
+    soft-masked (lowercase runs of ~500 bp); `n_run_per_mbp` runs of `n_run_len` N per Mbp; `n_empty` records with a title and no sequence
+    between the others. Returns bytes written."""
+    rng = np.random.default_rng(seed)
+    lens = [int(x) for x in contig_lens]
+    empty_before = np.bincount(rng.integers(0, len(lens) + 1, size=n_empty), minlength=len(lens) + 1)  # empty records in front of contig i
+    eol_a = np.frombuffer(eol, dtype=np.uint8)
+    chunk = line_width * (1 << 18)  # whole lines per chunk
+    total = 0
+    with open(path, "wb") as f:
+        for i in range(len(lens) + 1):
+            for j in range(int(empty_before[i])):
+                title = b">empty_%d_%d no sequence" % (i, j) + eol
+                f.write(title)
+                total += len(title)
+            if i == len(lens):
+                break
+            title = b">contig_%d synthetic assembly len=%d" % (i, lens[i]) + eol
+            f.write(title)
+            total += len(title)
+            for lo in range(0, lens[i], chunk):
+                m = min(chunk, lens[i] - lo)
+                seq = _ACGT[rng.integers(0, 4, size=m, dtype=np.uint8)]
+                if lower_frac > 0:
+                    n = int(rng.poisson(lower_frac * m / 500))
+                    d = np.zeros(m + 1, dtype=np.int32)
+                    st = rng.integers(0, m, size=n)
+                    np.add.at(d, st, 1)
+                    np.add.at(d, np.minimum(st + rng.integers(100, 900, size=n), m), -1)
+                    seq = np.where(np.cumsum(d[:m]) > 0, seq | 0x20, seq).astype(np.uint8)
+                if n_run_per_mbp > 0:
+                    for s0 in rng.integers(0, m, size=int(rng.poisson(n_run_per_mbp * m / 1e6))):
+                        seq[s0:s0 + n_run_len] = ord("N")
+                rows = (m + line_width - 1) // line_width
+                buf = np.zeros((rows, line_width + eol_a.size), dtype=np.uint8)
+                flat = np.zeros(rows * line_width, dtype=np.uint8)
+                flat[:m] = seq
+                buf[:, :line_width] = flat.reshape(rows, line_width)
+                buf[:, line_width:] = eol_a
+                out = buf.reshape(-1)
+                if m % line_width:  # the last line of the contig is short
+                    cut = (rows - 1) * (line_width + eol_a.size) + m % line_width
+                    out = np.concatenate([out[:cut], eol_a])
+                f.write(out.tobytes())
+                total += out.size
+    return total
+
+
 # Named configurations of BASELINE.json / SURVEY.md §8d
 CONFIGS = {
     "C1": dict(seed=12345, genome_len=400_000, n_reads=33_000),          # 10 MB FASTQ plumbing case
