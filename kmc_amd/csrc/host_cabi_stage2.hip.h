@@ -499,8 +499,6 @@ int kmc_hip_process_bins_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_par
 	return 0;
 }
 
-/* byte offsets of a bin's expander packs, appended to `ps` (first entry 0, last entry `size`): from the caller's pack sizes, or — none given — by one
- * walk over the image, a boundary every 4096 super-k-mers */
 /* Where the host-boundary calls spend their wall time, summed over all slots (KMC_HIP_VERBOSE prints them when the context is destroyed; the drop-in's workers sit in these
  * calls for most of stage 2 — profiles/r05/e2e_large_30gbp.json: 40 s summed over 16 workers for 0.73 s of kernels): [0] pack starts + buffers, [1] staging copy in (pageable
  * callers), [2] enqueue (copies + launches), [3] wait for the kernels (includes the H2D in front of them and every other slot's work queued before), [4] D2H of the exact-size
@@ -568,6 +566,8 @@ int kmc_hip_host_boundary_times(double seconds[8])
 	return 0;
 }
 
+/* byte offsets of a bin's expander packs, appended to `ps` (first entry 0, last entry `size`): from the caller's pack sizes, or — none given — by one
+ * walk over the image, a boundary every 4096 super-k-mers */
 static int append_pack_starts(const DevParams &P, const uint8_t *superkmers, u64 size, const uint64_t *pack_bytes, u64 n_packs, std::vector<u64> &ps)
 {
 	if (!size)
@@ -601,200 +601,8 @@ static int append_pack_starts(const DevParams &P, const uint8_t *superkmers, u64
 	return 0;
 }
 
-/* the kernels of the host-boundary bin whose image is in s.in, and the copy of its results block to pinned memory (caller holds s.mtx) */
-static int enqueue_host_bin(Slot &s, bool classic)
-{
-	const DevParams &P = s.sub_P;
-	if (int rc = run_bin_device(s, P, (const uint8_t *)s.in.p, s.sub_size, s.sub_n_rec, (const u64 *)s.pack_start.p, s.sub_np, (uint8_t *)s.out.p,
-	                            P.without_output ? 0 : s.out_capacity, nullptr /* out_bytes and stats: the slot's small block */, (u64 *)s.lut.p,
-	                            s.lut_entries, nullptr, classic))
-		return rc;
-	if (s.sub_n_rec == 0) /* the empty-bin path does not touch the small block */
-		HIPCHK(hipMemsetAsync(s.zero.p, 0, 64, s.stream));
-	HIPCHK(hipMemcpyAsync(small_ptr<u32>(s, SM_ERR), s.sticky.p, 4, hipMemcpyDeviceToDevice, s.stream));
-	HIPCHK(hipMemcpyAsync(s.h_res, s.zero.p, sizeof(HostRes), hipMemcpyDeviceToHost, s.stream));
-	HIPCHK(hipEventRecord(s.done_ev, s.stream));
-	return 0;
-}
-
-int kmc_hip_process_bin_submit(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_bin_params *params, const uint8_t *superkmers,
-                               uint64_t size, uint64_t n_rec, const uint64_t *pack_bytes, uint64_t n_packs, uint8_t *out_suffix,
-                               uint64_t out_capacity, uint64_t *lut)
-{
-	if (int rc = set_dev(ctx, dev))
-		return rc;
-	if (slot < 0 || slot >= N_SLOTS)
-		return fail(KMC_HIP_EINVAL, "slot out of range (see kmc_hip_num_slots)");
-	DevParams P;
-	if (int rc = check_params(params, P))
-		return rc;
-	Slot &s = ctx->devs[dev]->slot[slot];
-	std::lock_guard<std::mutex> lck(s.mtx);
-	SlabScope slab_scope(s.slab);
-	if (s.pending || s.hb_pending)
-		return fail(KMC_HIP_EINVAL, "slot already has a bin in flight");
-	if (size && !superkmers)
-		return fail(KMC_HIP_EINVAL, "superkmers == NULL");
-	const u64 lut_entries = P.kff ? 0 : kmc_hip_lut_entries(params);
-	if (!P.without_output && ((out_capacity && !out_suffix) || (lut_entries && !lut)))
-		return fail(KMC_HIP_EINVAL, "output buffers missing");
-
-	/* pack starts (byte offsets). Without packs from the caller, walk the image once on the host. */
-	HbLap lap;
-	++g_hb_ns[6];
-	std::vector<u64> &ps = s.h_pack_start;
-	ps.clear();
-	if (size) {
-		ps.push_back(0);
-		if (n_packs) {
-			u64 acc = 0;
-			for (u64 i = 0; i < n_packs; ++i) {
-				if (pack_bytes[i] == 0)
-					continue;
-				acc += pack_bytes[i];
-				ps.push_back(acc);
-			}
-			if (acc != size)
-				return fail(KMC_HIP_ECORRUPT, "sum of pack_bytes != size");
-		} else {
-			u64 pos = 0;
-			u32 in_pack = 0;
-			while (pos < size) {
-				const u32 e = superkmers[pos];
-				pos += 1 + (P.k + e + 3) / 4;
-				if (++in_pack == 4096 && pos < size) {
-					ps.push_back(pos);
-					in_pack = 0;
-				}
-			}
-			if (pos != size)
-				return fail(KMC_HIP_ECORRUPT, "super-k-mer stream is ragged");
-			ps.push_back(size);
-		}
-	}
-	const u64 np = ps.empty() ? 0 : ps.size() - 1;
-	int rc = 0;
-	if ((rc = ensure(s.in, size + 256)) || (rc = ensure(s.pack_start, (np + 1) * 8)) ||
-	    (rc = ensure(s.out, (P.without_output ? 0 : out_capacity) + 256)) || (rc = ensure(s.lut, lut_entries * 8 + 256)))
-		return rc;
-	lap.lap(0);
-	if (size) {
-		const void *src = superkmers;
-		if (!host_ptr_is_pinned(superkmers)) { /* pageable caller (the drop-in's arena): through the slot's pinned staging buffer */
-			if ((rc = ensure_pinned(s.h_stage_in, s.h_stage_in_cap, size)))
-				return rc;
-			memcpy(s.h_stage_in, superkmers, size);
-			src = s.h_stage_in;
-			lap.lap(1);
-		}
-		HIPCHK(hipMemcpyAsync(s.in.p, src, size, hipMemcpyHostToDevice, s.stream));
-		HIPCHK(hipMemsetAsync((char *)s.in.p + size, 0, 256, s.stream));
-		HIPCHK(hipMemcpyAsync(s.pack_start.p, ps.data(), (np + 1) * 8, hipMemcpyHostToDevice, s.stream));
-	}
-	/* staged when EITHER destination is ordinary memory (the records and the LUT may come from different allocations), as the several-bins path decides it */
-	s.out_staged = !P.without_output && ((out_capacity && !host_ptr_is_pinned((const void *)out_suffix)) || (lut_entries && !host_ptr_is_pinned((const void *)lut)));
-	s.timed = true;
-	s.sub_P = P;
-	s.sub_size = size;
-	s.sub_n_rec = n_rec;
-	s.sub_np = np;
-	s.out_capacity = out_capacity;
-	s.lut_entries = lut_entries;
-	if ((rc = enqueue_host_bin(s, false)))
-		return rc;
-	lap.lap(2);
-	s.pending = true;
-	s.h_out = out_suffix;
-	s.h_lut = (u64 *)lut;
-	s.out_capacity = out_capacity;
-	s.lut_entries = lut_entries;
-	s.without_output = P.without_output != 0;
-	return 0;
-}
-
-int kmc_hip_process_bin_wait(kmc_hip_ctx *ctx, int dev, int slot, uint64_t *out_bytes, uint64_t stats[4])
-{
-	if (int rc = set_dev(ctx, dev))
-		return rc;
-	if (slot < 0 || slot >= N_SLOTS)
-		return fail(KMC_HIP_EINVAL, "slot out of range (see kmc_hip_num_slots)");
-	Slot &s = ctx->devs[dev]->slot[slot];
-	std::lock_guard<std::mutex> lck(s.mtx);
-	SlabScope slab_scope(s.slab);
-	if (!s.pending)
-		return fail(KMC_HIP_EINVAL, "no bin in flight on this slot");
-	s.pending = false;
-	HbLap lap;
-	HIPCHK(hipEventSynchronize(s.done_ev)); /* blocks in the kernel driver instead of spinning */
-	if (int rc = harvest(s))
-		return rc;
-	lap.lap(3);
-	HostRes r = *s.h_res;
-	if (r.redo && !(r.err & ~KERR_CAPACITY)) { /* the hybrid sort met a tile it could not handle: the bin again (its image is still in s.in), LSD passes over every byte.
-		                                      * A capacity error of the first attempt does not count: a tile that was handed back may have been compacted unsorted */
-		note_redo();
-		raise_top();
-		if (r.err)
-			if (int rc = clear_sticky(s, r.err))
-				return rc;
-		if (int rc = enqueue_host_bin(s, true))
-			return rc;
-		HIPCHK(hipEventSynchronize(s.done_ev));
-		r = *s.h_res;
-		++g_hb_ns[7];
-		lap.lap(3);
-	}
-	if (r.err) {
-		if (int rc = clear_sticky(s, r.err))
-			return rc;
-		return err_to_code(r.err);
-	}
-	if (r.out_bytes > s.out_capacity)
-		return fail(KMC_HIP_ECAPACITY, "out_capacity too small for the counted k-mers");
-	if (!s.without_output) {
-		/* exact-size copies: out_bytes is only known now (the capacity is ~10x the counted bytes at the default cutoffs) */
-		uint8_t *dst_out = s.h_out;
-		u64 *dst_lut = s.h_lut;
-		const size_t lut_bytes = (size_t)s.lut_entries * 8;
-		if (s.out_staged) { /* pageable caller: records and LUT land in the slot's pinned staging buffer and are copied on from there */
-			if (int rc = ensure_pinned(s.h_stage_out, s.h_stage_out_cap, r.out_bytes + lut_bytes + 16))
-				return rc;
-			dst_lut = (u64 *)s.h_stage_out;
-			dst_out = (uint8_t *)s.h_stage_out + lut_bytes;
-		}
-		if (r.out_bytes)
-			HIPCHK(hipMemcpyAsync(dst_out, s.out.p, r.out_bytes, hipMemcpyDeviceToHost, s.stream));
-		if (s.lut_entries)
-			HIPCHK(hipMemcpyAsync(dst_lut, s.lut.p, lut_bytes, hipMemcpyDeviceToHost, s.stream));
-		HIPCHK(hipEventRecord(s.done_ev, s.stream));
-		HIPCHK(hipEventSynchronize(s.done_ev));
-		lap.lap(4);
-		if (s.out_staged) {
-			if (r.out_bytes)
-				memcpy(s.h_out, dst_out, r.out_bytes);
-			if (lut_bytes)
-				memcpy(s.h_lut, dst_lut, lut_bytes);
-			lap.lap(5);
-		}
-	}
-	if (out_bytes)
-		*out_bytes = r.out_bytes;
-	if (stats)
-		for (int i = 0; i < 4; ++i)
-			stats[i] = r.stats[i];
-	return 0;
-}
-
-int kmc_hip_process_bin(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_params *params, const uint8_t *superkmers, uint64_t size,
-                        uint64_t n_rec, const uint64_t *pack_bytes, uint64_t n_packs, uint8_t *out_suffix, uint64_t out_capacity,
-                        uint64_t *out_bytes, uint64_t *lut, uint64_t stats[4])
-{
-	if (int rc = kmc_hip_process_bin_submit(ctx, dev, 0, params, superkmers, size, n_rec, pack_bytes, n_packs, out_suffix, out_capacity, lut))
-		return rc;
-	return kmc_hip_process_bin_wait(ctx, dev, 0, out_bytes, stats);
-}
-
-/* ---- host-boundary GROUPS: up to HB_MAX bins per call, sorted together like the bins of kmc_hip_process_bins_device ---- */
+/* ---- the host boundary: 1..HB_MAX bins per call, sorted together like the bins of kmc_hip_process_bins_device. One bin per call (kmc_hip_process_bin_submit/_wait)
+ * is the group of one: no tag bits, hence the keys, passes and kernels of a bin on its own ---- */
 static int hb_enqueue_results(Slot &s)
 {
 	HbRes *res = (HbRes *)s.hb_res.p;
@@ -804,29 +612,17 @@ static int hb_enqueue_results(Slot &s)
 	return 0;
 }
 
-int kmc_hip_process_bins_submit(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_bin_params *params, const kmc_hip_host_bin *bins, uint32_t n_bins)
+/* caller holds s.mtx inside the slot's slab scope; `call`: the entry, whose _wait collects */
+static int hb_submit_locked(Slot &s, const DevParams &P, u64 lut_entries, const kmc_hip_host_bin *bins, u32 n_bins, Slot::HbCall call)
 {
-	if (int rc = set_dev(ctx, dev))
-		return rc;
-	if (slot < 0 || slot >= N_SLOTS)
-		return fail(KMC_HIP_EINVAL, "slot out of range (see kmc_hip_num_slots)");
-	DevParams P;
-	if (int rc = check_params(params, P))
-		return rc;
-	if (!bins || n_bins < 1 || n_bins > HB_MAX)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_process_bins_submit: 1..16 bins per call");
-	Slot &s = ctx->devs[dev]->slot[slot];
-	std::lock_guard<std::mutex> lck(s.mtx);
-	SlabScope slab_scope(s.slab);
-	if (s.pending || s.hb_pending)
+	if (s.hb_call != Slot::HB_NONE)
 		return fail(KMC_HIP_EINVAL, "slot already has a bin in flight");
-	const u64 lut_entries = P.kff ? 0 : kmc_hip_lut_entries(params);
 	const u64 lut_pitch = up256(lut_entries * 8);
 	HbLap lap;
 	++g_hb_ns[6];
 	std::vector<u64> &ps = s.h_pack_start;
 	ps.clear();
-	std::vector<u64> in_off(n_bins), out_off(n_bins), ps_off(n_bins), np(n_bins);
+	u64 in_off[HB_MAX], out_off[HB_MAX], ps_off[HB_MAX], np[HB_MAX];
 	u64 in_total = 0, out_total = 0, recs = 0;
 	for (u32 i = 0; i < n_bins; ++i) {
 		const kmc_hip_host_bin &b = bins[i];
@@ -848,18 +644,14 @@ int kmc_hip_process_bins_submit(kmc_hip_ctx *ctx, int dev, int slot, const kmc_h
 	}
 	int rc = 0;
 	if ((rc = ensure(s.in, in_total + 256)) || (rc = ensure(s.pack_start, (ps.size() + 1) * 8)) || (rc = ensure(s.out, out_total + 256)) ||
-	    (rc = ensure(s.lut, (u64)n_bins * lut_pitch + 256)) || (rc = ensure(s.hb_res, sizeof(HbRes))))
+	    (rc = ensure(s.lut, (u64)n_bins * lut_pitch + 256)))
 		return rc;
-	if (!s.h_hb_res)
-		HIPCHK(hipHostMalloc((void **)&s.h_hb_res, sizeof(HbRes), hipHostMallocDefault));
 	HbRes *res = (HbRes *)s.hb_res.p;
-	HIPCHK(hipMemsetAsync(res, 0, sizeof(HbRes), s.stream));
-	if (!ps.empty())
-		HIPCHK(hipMemcpyAsync(s.pack_start.p, ps.data(), ps.size() * 8, hipMemcpyHostToDevice, s.stream));
 	s.hb.resize(n_bins);
 	bool stage_in = false;
 	s.out_staged = false;
-	for (u32 i = 0; i < n_bins; ++i) { /* one pageable buffer among the call's: everything of the call goes through the pinned staging buffers */
+	for (u32 i = 0; i < n_bins; ++i) { /* one pageable buffer among the call's (the drop-in's arena; the records and the LUT of a bin may come from different allocations):
+		                                 * everything of the call goes through the slot's pinned staging buffers */
 		stage_in = stage_in || (bins[i].size && !host_ptr_is_pinned(bins[i].superkmers));
 		if (!P.without_output)
 			s.out_staged = s.out_staged || (bins[i].out_capacity && !host_ptr_is_pinned(bins[i].out_suffix)) || (lut_entries && !host_ptr_is_pinned(bins[i].lut));
@@ -894,6 +686,11 @@ int kmc_hip_process_bins_submit(kmc_hip_ctx *ctx, int dev, int slot, const kmc_h
 		h.h_out = b.out_suffix;
 		h.h_lut = (u64 *)b.lut;
 	}
+	/* behind the images, not in front of them: a call opens with a copy, which no kernel of another slot on the same hardware queue holds back (measured, DESIGN.md §8:
+	 * with this memset first the one-bin leg of bench.py fell from 31.2-31.7 to 26.6-26.8 Gk-mers/s) */
+	HIPCHK(hipMemsetAsync(res, 0, sizeof(HbRes), s.stream));
+	if (!ps.empty())
+		HIPCHK(hipMemcpyAsync(s.pack_start.p, ps.data(), ps.size() * 8, hipMemcpyHostToDevice, s.stream));
 	/* sort groups: as many consecutive bins as the spare bits of the top digit can tag (group_capacity), while the record array stays moderate */
 	const u32 G = group_capacity(P.k, recs / n_bins < GROUP_SMALL_BIN_RECORDS);
 	const u64 rec_bytes_of = (u64)((P.k + 31) / 32) * 8;
@@ -921,24 +718,18 @@ int kmc_hip_process_bins_submit(kmc_hip_ctx *ctx, int dev, int slot, const kmc_h
 	if ((rc = hb_enqueue_results(s)))
 		return rc;
 	lap.lap(2);
-	s.hb_pending = true;
+	s.hb_call = call;
 	return 0;
 }
 
-int kmc_hip_process_bins_wait(kmc_hip_ctx *ctx, int dev, int slot, uint64_t *out_bytes, uint64_t *stats)
+/* caller holds s.mtx inside the slot's slab scope; out_bytes[bins] and stats[bins][4] of the call, either may be NULL */
+static int hb_wait_locked(Slot &s, Slot::HbCall call, u64 *out_bytes, u64 *stats)
 {
-	if (int rc = set_dev(ctx, dev))
-		return rc;
-	if (slot < 0 || slot >= N_SLOTS)
-		return fail(KMC_HIP_EINVAL, "slot out of range (see kmc_hip_num_slots)");
-	Slot &s = ctx->devs[dev]->slot[slot];
-	std::lock_guard<std::mutex> lck(s.mtx);
-	SlabScope slab_scope(s.slab);
-	if (!s.hb_pending)
-		return fail(KMC_HIP_EINVAL, "no group of bins in flight on this slot");
-	s.hb_pending = false;
+	if (s.hb_call != call)
+		return fail(KMC_HIP_EINVAL, call == Slot::HB_ONE_BIN ? "no bin in flight on this slot" : "no group of bins in flight on this slot");
+	s.hb_call = Slot::HB_NONE;
 	HbLap lap;
-	HIPCHK(hipEventSynchronize(s.done_ev));
+	HIPCHK(hipEventSynchronize(s.done_ev)); /* blocks in the kernel driver instead of spinning */
 	if (int rc = harvest(s))
 		return rc;
 	lap.lap(3);
@@ -982,10 +773,10 @@ int kmc_hip_process_bins_wait(kmc_hip_ctx *ctx, int dev, int slot, uint64_t *out
 	for (size_t i = 0; i < n; ++i)
 		if (r.w[i][0] > s.hb[i].d.out_capacity && !s.without_output)
 			return fail(KMC_HIP_ECAPACITY, "out_capacity too small for the counted k-mers");
-	if (!s.without_output) { /* exact-size copies */
+	if (!s.without_output) { /* exact-size copies: out_bytes is only known now (the capacity is ~10x the counted bytes at the default cutoffs) */
 		const size_t lut_bytes = (size_t)s.lut_entries * 8;
-		std::vector<size_t> off(n + 1, 0);
-		if (s.out_staged) {
+		size_t off[HB_MAX + 1] = {0};
+		if (s.out_staged) { /* pageable caller: records and LUTs land in the slot's pinned staging buffer and are copied on from there */
 			for (size_t i = 0; i < n; ++i)
 				off[i + 1] = off[i] + (((size_t)r.w[i][0] + lut_bytes + 63) & ~(size_t)63);
 			if (int rc = ensure_pinned(s.h_stage_out, s.h_stage_out_cap, off[n] + 64))
@@ -1022,6 +813,74 @@ int kmc_hip_process_bins_wait(kmc_hip_ctx *ctx, int dev, int slot, uint64_t *out
 	return 0;
 }
 
+int kmc_hip_process_bin_submit(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_bin_params *params, const uint8_t *superkmers,
+                               uint64_t size, uint64_t n_rec, const uint64_t *pack_bytes, uint64_t n_packs, uint8_t *out_suffix,
+                               uint64_t out_capacity, uint64_t *lut)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	if (slot < 0 || slot >= N_SLOTS)
+		return fail(KMC_HIP_EINVAL, "slot out of range (see kmc_hip_num_slots)");
+	DevParams P;
+	if (int rc = check_params(params, P))
+		return rc;
+	const kmc_hip_host_bin bin = {superkmers, size, n_rec, pack_bytes, n_packs, out_suffix, out_capacity, lut};
+	Slot &s = ctx->devs[dev]->slot[slot];
+	std::lock_guard<std::mutex> lck(s.mtx);
+	SlabScope slab_scope(s.slab);
+	return hb_submit_locked(s, P, P.kff ? 0 : kmc_hip_lut_entries(params), &bin, 1, Slot::HB_ONE_BIN);
+}
+
+int kmc_hip_process_bin_wait(kmc_hip_ctx *ctx, int dev, int slot, uint64_t *out_bytes, uint64_t stats[4])
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	if (slot < 0 || slot >= N_SLOTS)
+		return fail(KMC_HIP_EINVAL, "slot out of range (see kmc_hip_num_slots)");
+	Slot &s = ctx->devs[dev]->slot[slot];
+	std::lock_guard<std::mutex> lck(s.mtx);
+	SlabScope slab_scope(s.slab);
+	return hb_wait_locked(s, Slot::HB_ONE_BIN, (u64 *)out_bytes, (u64 *)stats);
+}
+
+int kmc_hip_process_bin(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_params *params, const uint8_t *superkmers, uint64_t size,
+                        uint64_t n_rec, const uint64_t *pack_bytes, uint64_t n_packs, uint8_t *out_suffix, uint64_t out_capacity,
+                        uint64_t *out_bytes, uint64_t *lut, uint64_t stats[4])
+{
+	if (int rc = kmc_hip_process_bin_submit(ctx, dev, 0, params, superkmers, size, n_rec, pack_bytes, n_packs, out_suffix, out_capacity, lut))
+		return rc;
+	return kmc_hip_process_bin_wait(ctx, dev, 0, out_bytes, stats);
+}
+
+int kmc_hip_process_bins_submit(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_bin_params *params, const kmc_hip_host_bin *bins, uint32_t n_bins)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	if (slot < 0 || slot >= N_SLOTS)
+		return fail(KMC_HIP_EINVAL, "slot out of range (see kmc_hip_num_slots)");
+	DevParams P;
+	if (int rc = check_params(params, P))
+		return rc;
+	if (!bins || n_bins < 1 || n_bins > HB_MAX)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_process_bins_submit: 1..16 bins per call");
+	Slot &s = ctx->devs[dev]->slot[slot];
+	std::lock_guard<std::mutex> lck(s.mtx);
+	SlabScope slab_scope(s.slab);
+	return hb_submit_locked(s, P, P.kff ? 0 : kmc_hip_lut_entries(params), bins, n_bins, Slot::HB_GROUP);
+}
+
+int kmc_hip_process_bins_wait(kmc_hip_ctx *ctx, int dev, int slot, uint64_t *out_bytes, uint64_t *stats)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	if (slot < 0 || slot >= N_SLOTS)
+		return fail(KMC_HIP_EINVAL, "slot out of range (see kmc_hip_num_slots)");
+	Slot &s = ctx->devs[dev]->slot[slot];
+	std::lock_guard<std::mutex> lck(s.mtx);
+	SlabScope slab_scope(s.slab);
+	return hb_wait_locked(s, Slot::HB_GROUP, (u64 *)out_bytes, (u64 *)stats);
+}
+
 int kmc_hip_process_bin_multi(kmc_hip_ctx *ctx, const kmc_hip_bin_params *params, const uint8_t *superkmers, uint64_t size, uint64_t n_rec,
                               const uint64_t *pack_bytes, uint64_t n_packs, uint8_t *out_suffix, uint64_t out_capacity, uint64_t *out_bytes, uint64_t *lut,
                               uint64_t stats[4])
@@ -1047,27 +906,9 @@ int kmc_hip_process_bin_multi(kmc_hip_ctx *ctx, const kmc_hip_bin_params *params
 			memset(lut, 0, lut_entries * 8);
 		return 0;
 	}
-	std::vector<u64> ps(1, 0);
-	if (n_packs) {
-		for (u64 i = 0; i < n_packs; ++i)
-			if (pack_bytes[i])
-				ps.push_back(ps.back() + pack_bytes[i]);
-		if (ps.back() != size)
-			return fail(KMC_HIP_ECORRUPT, "sum of pack_bytes != size");
-	} else {
-		u64 pos = 0;
-		u32 in_pack = 0;
-		while (pos < size) {
-			pos += 1 + (P.k + superkmers[pos] + 3) / 4;
-			if (++in_pack == 4096 && pos < size) {
-				ps.push_back(pos);
-				in_pack = 0;
-			}
-		}
-		if (pos != size)
-			return fail(KMC_HIP_ECORRUPT, "super-k-mer stream is ragged");
-		ps.push_back(size);
-	}
+	std::vector<u64> ps;
+	if (int rc = append_pack_starts(P, superkmers, size, pack_bytes, n_packs, ps))
+		return rc;
 	switch ((P.k + 31) / 32) {
 	case 1: return process_bin_multi_t<1>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
 	case 2: return process_bin_multi_t<2>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);

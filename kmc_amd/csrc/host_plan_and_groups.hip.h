@@ -862,7 +862,8 @@ constexpr u64 GROUP_MAX_RECORD_BYTES = 6ull << 30; /* per record array of a grou
                               * k = 55 21.3 -> 22.7 (16-byte gathers waste half of every HBM sector: finisher 1.81 -> 2.91 ms, passes 3.92 -> 2.20) */
 #endif
 
-/* d_stats / d_out_bytes == NULL in a descriptor (groups of one only): the slot's own small block (host-boundary path) */
+/* d_stats / d_out_bytes == NULL in a descriptor (groups of one only): the slot's own small block. No caller passes NULL any more (the host
+ * boundary writes to its HbRes block; the multi-device bin and the compaction hook fill their BinPlan themselves): the fallbacks below can go */
 template <int SIZE>
 int run_group_device_t(Slot &s, const DevParams &P, const kmc_hip_bin_desc *const *descs, u32 g, u64 lut_entries, bool classic, u32 *d_flag, bool *used_hybrid)
 {

@@ -133,7 +133,7 @@ int ensure_pinned(void *&p, size_t &cap, size_t bytes)
 /* bytes 0..15: unused */
 constexpr size_t SM_STATS = 16;      /* u64[4]                           */
 constexpr size_t SM_OUTBYTES = 48;   /* u64                              */
-constexpr size_t SM_ERR = 56;        /* u32: copy of the slot's sticky error word, taken when a host-boundary bin ends */
+/* bytes 56..59: unused */
 constexpr size_t SM_REDO = 60;       /* u32: set by the LDS finisher when a tile of the hybrid sort did not fit: the host sorts the group again, LSD over all bytes */
 constexpr size_t SM_DBASE_WORK = 256; /* u64[2][256] per-portion digit bases (ping-pong) */
 constexpr size_t SM_COUNTERS = 256 + 2 * 256 * 8; /* u32[N_COUNTERS] ticket counters, one per launch (the tally shards of the compaction are per bin, BinPlan) */
@@ -152,7 +152,7 @@ constexpr u64 PORTION_MAX = 1ull << 29; /* records per scatter launch (30-bit lo
  * oracle-checkable sort crosses many portion boundaries (digit bases carried from launch to launch) — the path a bin of
  * more than 2^29 k-mers takes. */
 
-struct HostRes {
+struct HostRes { /* the head of the small block, as the multi-device bin and the compaction hook read it back */
 	u64 totals[2];
 	u64 stats[4];
 	u64 out_bytes;
@@ -170,8 +170,8 @@ struct ZeroPlan {
 };
 inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-/* results of a host-boundary GROUP (kmc_hip_process_bins_submit): per bin out_bytes + the four tallies, per sort group the hybrid sort's "again"
- * word, the stream's sticky error word — one block on the device, copied to pinned memory when the group's kernels are done */
+/* results of a host-boundary call (kmc_hip_process_bin_submit: one bin; kmc_hip_process_bins_submit: up to HB_MAX): per bin out_bytes + the four tallies, per
+ * sort group the hybrid sort's "again" word, the stream's sticky error word — one block on the device, copied to pinned memory when the call's kernels are done */
 constexpr u32 HB_MAX = 16;
 struct HbRes {
 	u64 w[HB_MAX][8]; /* [0] out_bytes, [1..4] stats */
@@ -189,7 +189,6 @@ struct Slot {
 	DBuf bounds;   /* hybrid sort: tile boundaries of k_bucket_bounds, u64[windows + 1] */
 	DBuf arena_work; /* rank groups of one-word records: entries, offsets, bucket numbers, heavy chunks, digit bases and look-back rows of the arena's passes (the arenas: pairA / pairB) */
 	DBuf redo_log; /* hybrid sort: one "sort me again" word per asynchronous group since the last drain (drain_redo) */
-	HostRes *h_res = nullptr; /* pinned */
 	/* pinned staging for callers whose buffers are ordinary (pageable) memory — the drop-in worker's arena: a copy straight from / to such memory makes the
 	 * runtime pin the caller's pages on the fly, and the unmapping of an arena that has been pinned piecewise costs twice as much at the end of KMC's stage 2
 	 * (tools/ubench_munmap_hip.py: 0.23 s instead of 0.12 s for 2.3 GB; nothing left after a parallel MADV_DONTNEED only when nothing was ever pinned) */
@@ -208,16 +207,6 @@ struct Slot {
 	u64 sc_keys_total = 0, sc_launch_total = 0, ls_keys_total = 0, ls_launch_total = 0;
 	bool timed = false;
 	u32 async_seq = 0; /* asynchronous device-resident bins on this slot: every TIMING_SAMPLE-th one carries events */
-	/* pending async bin */
-	bool pending = false;
-	uint8_t *h_out = nullptr;
-	u64 *h_lut = nullptr;
-	u64 out_capacity = 0, lut_entries = 0;
-	bool without_output = false;
-	std::vector<u64> h_pack_start;
-	/* host-boundary bin in flight: what a redo needs */
-	DevParams sub_P = {};
-	u64 sub_size = 0, sub_n_rec = 0, sub_np = 0;
 	/* asynchronous device-resident groups since the last drain, in redo_log order */
 	struct PendingGroup {
 		DevParams P;
@@ -225,7 +214,9 @@ struct Slot {
 		std::vector<kmc_hip_bin_desc> descs;
 	};
 	std::vector<PendingGroup> pending_groups;
-	/* host-boundary group in flight */
+	/* host-boundary call in flight — one bin (kmc_hip_process_bin_submit) or a group of bins (kmc_hip_process_bins_submit): what _wait and a redo need */
+	enum HbCall { HB_NONE, HB_ONE_BIN, HB_GROUP };
+	HbCall hb_call = HB_NONE; /* the entry that submitted: its _wait alone may collect (the callers' result arrays differ in length) */
 	struct HostBin {
 		kmc_hip_bin_desc d; /* device side */
 		uint8_t *h_out;
@@ -234,10 +225,12 @@ struct Slot {
 	std::vector<HostBin> hb;
 	std::vector<std::pair<u32, u32>> hb_chunks; /* (first bin, bins) of every sort group */
 	std::vector<char> hb_hybrid;
-	DBuf hb_res;
+	std::vector<u64> h_pack_start;
+	DBuf hb_res;               /* both from slot_init: no allocation at the moment stage 2 starts */
 	HbRes *h_hb_res = nullptr; /* pinned */
 	DevParams hb_P = {};
-	bool hb_pending = false;
+	u64 lut_entries = 0;
+	bool without_output = false;
 };
 
 struct Dev {
@@ -308,8 +301,10 @@ int slot_init(Slot &s, u64 portion)
 {
 	s.portion = portion;
 	HIPCHK(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-	HIPCHK(hipHostMalloc((void **)&s.h_res, sizeof(HostRes), hipHostMallocDefault));
-	memset(s.h_res, 0, sizeof(HostRes));
+	HIPCHK(hipHostMalloc((void **)&s.h_hb_res, sizeof(HbRes), hipHostMallocDefault));
+	memset(s.h_hb_res, 0, sizeof(HbRes));
+	if (int rc = ensure(s.hb_res, sizeof(HbRes)))
+		return rc;
 	for (auto &e : s.ev)
 		HIPCHK(hipEventCreate(&e));
 	HIPCHK(hipEventCreateWithFlags(&s.done_ev, hipEventBlockingSync | hipEventDisableTiming));
@@ -329,8 +324,6 @@ void slot_destroy(Slot &s)
 			(void)hipFree(b->p);
 	if (s.slab.p)
 		(void)hipFree(s.slab.p);
-	if (s.h_res)
-		(void)hipHostFree(s.h_res);
 	if (s.h_hb_res)
 		(void)hipHostFree(s.h_hb_res);
 	if (s.h_stage_in)

@@ -861,6 +861,10 @@ def test_host_boundary_group_redo_errors_and_slot_reuse(ctx):
         w = O.process_bin(op(p55), b[0], b[1])
         assert all(np.array_equal(x, y) for x, y in zip(got[i], w)), i
     assert ctx.local_sort_totals()["redo_groups"] > r0
+    r0 = ctx.local_sort_totals()["redo_groups"]  # ... and one of them through the one-bin entry: the same redo, inside kmc_hip_process_bin_wait
+    got1 = ctx.process_bin(p55, bins[0][0], bins[0][1], bins[0][2])
+    assert all(np.array_equal(x, y) for x, y in zip(got1, O.process_bin(op(p55), bins[0][0], bins[0][1])))
+    assert ctx.local_sort_totals()["redo_groups"] > r0
     bins = capi.synth_bins(seed=5, genome_len=300, n_reads=20_000 if not small else 1500, k=27, n_bins=3, err=0.0)
     p = hp(27)
     img, nk, packs = binsynth.random_bin(np.random.default_rng(1), 27, 500, max_extra=20)

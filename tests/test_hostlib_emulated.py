@@ -154,6 +154,11 @@ for i, b in enumerate(bins):
     w = O.process_bin(O.make_params(55), b[0], b[1])
     assert np.array_equal(got[i][0], w[0]) and np.array_equal(got[i][1], w[1]) and np.array_equal(got[i][2], w[2]), i
 assert ctx.local_sort_totals()["redo_groups"] > before
+before = ctx.local_sort_totals()["redo_groups"]  # ... and one of them through the one-bin entry: the same redo, inside kmc_hip_process_bin_wait
+got1 = ctx.process_bin(capi.make_params(55), bins[0][0], bins[0][1], bins[0][2])
+w = O.process_bin(O.make_params(55), bins[0][0], bins[0][1])
+assert np.array_equal(got1[0], w[0]) and np.array_equal(got1[1], w[1]) and np.array_equal(got1[2], w[2])
+assert ctx.local_sort_totals()["redo_groups"] > before
 rng = np.random.default_rng(3)
 a = rng.integers(0, 2**54, size=(5000, 1), dtype=np.uint64)
 assert np.array_equal(ctx.sort_records(a, 7), O.sort(a))
