@@ -16,7 +16,7 @@
  *   k_onesweep_dyn   the library's own 8-bit LSD pass (kernels.hip.h), ceil((rbits + bits of the last ordinal) / 8) times over the arena: all 256 CUs, stable, blind to
  *                    what the digits look like. The arena ends ordered by (entry, key)
  *   k_arena_finish   per work item. A bucket that fits a tile (kind 1) goes back to its place in the group's array, in order — its tile is ranked and counted afterwards
- *                    by k_bucket_rank_heavy, which leaves such a bucket where it lies. A giant bucket (kind 0) is counted from the arena, cut into segments that report
+ *                    by k_bucket_rank (bucket_sort.hip.h br_tile), which leaves such a bucket where it lies. A giant bucket (kind 0) is counted from the arena, cut into segments that report
  *                    into the output slots of the windows the bucket covers (those windows hold no tile: nothing else starts in them), each segment by one workgroup:
  *                    run tails, counts (a run may reach back over segments: one 64-ary search), cutoffs, records, LUT, tallies — what k_giant_tiles did for a whole tile
  *                    with one workgroup.
@@ -369,7 +369,7 @@ __global__ void __launch_bounds__(AF_THREADS) k_arena_finish(const GrpRank gr, c
 		const u32 len = en.len;
 		const u64 *__restrict__ B = src + off; /* the bucket, in order */
 		const u64 khi = rbits < 64 ? aw.bucket_hi[e] << rbits : 0ull; /* the key bits above rbits */
-		if ((en.w0 >> 44) & 1ull) { /* back to where it came from, in order; k_bucket_rank_heavy takes the tile from there */
+		if ((en.w0 >> 44) & 1ull) { /* back to where it came from, in order; k_bucket_rank takes the tile from there */
 			u64 *dst = const_cast<u64 *>(aw.S0) + gpos;
 			for (u32 i = tid; i < len; i += THREADS)
 				dst[i] = khi | (B[i] & rmask);

@@ -16,6 +16,8 @@ EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
 # slow) and a small one (128/256-thread workgroups, 4 KB expand slices) that runs the same code paths ~10x faster. Tests use the small one
 # unless they ask for "product".
 GEOMETRY_FLAGS = {"small": ["-DCP_BLOCK_THREADS=128", "-DEXP_BLOCK_THREADS=256", "-DEXP_CHUNK_BYTES=4096", "-DRS_BLOCK_THREADS=256", "-DCP_FOLD_CHUNK=256", "-DS1_SK_TILE_N=64", "-DS1_PACK_BYTES_N=16384", "-DS1_SUB_N=2", "-DBS_BLOCK_THREADS=128", "-DBC_BLOCK_THREADS=128", "-DBR_THREADS=128", "-DGT_THREADS=256", "-DGT_MAX_RECORDS_LOG2=11", "-DAR_THREADS=256", "-DBR_MID=192", "-DBD_STRIDE_N=88"], "product": []}
+# the small geometry with the detector's inequality as tight as in the product (BR_MID + 1 == 2 BD_STRIDE; the product: 352 = 2 x 176): tests/plantbins.py
+GEOMETRY_FLAGS["small_tight"] = [f for f in GEOMETRY_FLAGS["small"] if not f.startswith("-DBR_MID=")] + ["-DBR_MID=175"]
 _LIBS = {}
 
 

@@ -13,6 +13,7 @@ import pytest
 import binsynth
 import golden_io
 import oracle_py as O
+import plantbins
 from kmc_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -1155,3 +1156,47 @@ def test_rank_path_big_buckets_of_two_word_records(monkeypatch):
             assert all(np.array_equal(a, b) for a, b in zip(got[i], w)), i
     finally:
         ctx.close()
+
+
+# ------------------------------------------------------------------------------------------------ planted buckets on the detector's sample grid
+@pytest.mark.parametrize("case", plantbins.CASES)
+def test_planted_buckets_at_every_offset_of_the_detector_grid(ctx, case):
+    """The trust boundary of round 6 for one-word records: br_tile (bucket_sort.hip.h) gives every record of a bucket beyond BR_MID records the place it lies at and never
+    compares it again — right only if k_bucket_detect (arena_sort.hip.h) listed that bucket from its samples (one record per BD_STRIDE; BR_MID + 1 == 2 BD_STRIDE in the
+    product: a bucket of BR_MID + 1 records shows in exactly two samples) and the arena put it in order. A miss raises no flag: it is wrong output. tests/plantbins.py plants
+    buckets of chosen lengths — BR_MID - 11 .. BR_MID + 14, BD_STRIDE, BD_STRIDE + 1, 2 BD_STRIDE - 1, 2 BD_STRIDE, CAP, CAP + 1 on the device; a thinner set on the emulated
+    library — at EVERY start residue of the sample grid, in shuffled bins (a missed bucket stays in arrival order), and at the named places: a bin's first and last record,
+    the seam between two detect blocks (edge_n / edge_p), window seams and both chunks of a chunked tile, CAP / CAP + 1 on a window's first and last record (one and three
+    segments in k_arena_plan), a giant bucket whose one long run reaches back over two segments of k_arena_finish under cutoff_max / counter_max; k = 21 / 25 (9-16 bins per
+    group) / 32, both strands, KFF, without output. Exact: records, LUT and statistics per bin equal the oracle's; no redo, no LSD group; the giant counters equal the planted
+    buckets beyond CAP. (In the product's geometry a second chunk is one bucket of more than CAP - S = 512 > BR_MID records: "an untrusted second chunk behind a trusted
+    bucket" exists, and is planted, only where CAP - S < BR_MID — the emulated geometries.)"""
+    kind = capi.backend_kind()
+    geo = plantbins.geometry_of(kind, capi.lib_path())
+    k, kw, bins, planted, ordered, rbits = plantbins.make_case(geo, case, device=kind == 0)
+    n_planted, n_rec = sum(len(pl) for pl in planted), sum(b[1] for b in bins)
+    print(f"planted[{case}] {geo} rbits {rbits}: {len(bins)} bins, {n_planted} planted buckets, {n_rec} records")
+    assert all(b[1] > geo.CAP for b in bins) or case == "short-last-bin-k27"
+    p = capi.make_params(k, **kw)
+    op_ = op(p)
+    t0, c0 = ctx.local_sort_totals(reset=False), ctx.path_counters()
+    got, err = _run_batch(ctx, p, bins, 1)
+    t1, c1 = ctx.local_sort_totals(reset=False), ctx.path_counters()
+    assert err is None, err
+    rec = ctx.out_rec_bytes(p)
+    for i, (img, nrec, packs, _) in enumerate(bins):
+        w = O.process_bin(op_, img, nrec)
+        same = [np.array_equal(a, b) for a, b in zip(got[i], w)]
+        if not all(same):
+            d = _first_diff(got[i][0], w[0])
+            j = int(np.flatnonzero(got[i][0][:min(got[i][0].size, w[0].size)] != w[0][:min(got[i][0].size, w[0].size)])[:1].sum()) // max(rec, 1)
+            where = plantbins.locate(geo, planted[i], ordered[i], j, p.cutoff_min, p.cutoff_max)
+            dump = os.environ.get("KMC_PLANT_DUMP_DIR")
+            if dump:
+                np.savez(os.path.join(dump, f"planted_{case}_bin{i}.npz"), image=img, got_out=got[i][0], want_out=w[0], got_lut=got[i][1], want_lut=w[1], got_stats=got[i][2],
+                         want_stats=w[2], planted=np.array([(f, L) for f, L, _ in planted[i]]))
+            raise AssertionError(f"{case}: bin {i} of {len(bins)} differs from the oracle (records, LUT, statistics equal: {same}); statistics {got[i][2]} / {w[2]}; first "
+                                 f"difference {d}, output record {j}: {where}; redo {t1['redo_groups'] - t0['redo_groups']}")
+    assert t1["redo_groups"] == t0["redo_groups"] and c1["lsd"] == c0["lsd"] and c1["rank_count"] > c0["rank_count"], (t0, t1, c0, c1)
+    g_n, g_rec = plantbins.n_giant(geo, planted)
+    assert (c1["giant_tiles"] - c0["giant_tiles"], c1["giant_records"] - c0["giant_records"]) == (g_n, g_rec), (c0, c1, g_n, g_rec)

@@ -278,3 +278,25 @@ def test_dropin_host_side_switches_of_round_6_keep_the_database(tmp_path):
         assert got[:2] == want[:2], tag
         if tag == "slab-1MB":
             assert "stream slots have a slab of 1 MB" in got[2], got[2][-600:]
+
+
+@pytest.mark.parametrize("geometry", ["small", "small_tight"])
+def test_planted_bucket_sweep_on_the_emulated_host_library(geometry):
+    """test_planted_buckets_at_every_offset_of_the_detector_grid (test_gpu_parity.py, tests/plantbins.py) on the CPU: buckets planted at every start residue of
+    k_bucket_detect's sample grid and at the named seams, through the emulated host library in two geometries — `small` (BR_MID 192 over a stride of 88: 17 records of
+    slack) and `small_tight` (BR_MID 175: BR_MID + 1 == 2 BD_STRIDE, the product's own tight case, which `small` cannot reach). Every case must PASS in the child: a child
+    that selects nothing, skips or fails a case fails here."""
+    import plantbins
+
+    lib = emu.build_hostlib(geometry)
+    assert os.path.basename(lib) == f"libkmc_hip_emu_{geometry}.so"
+    env = dict(os.environ, KMC_HIP_LIB=lib, KMC_PLANT_GEOMETRY=geometry)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-q", "-p", "no:cacheprovider", "-rA",
+                        "-k", "test_planted_buckets_at_every_offset_of_the_detector_grid"], env=env, capture_output=True, text=True, timeout=3000, cwd=ROOT)
+    text = r.stdout + r.stderr
+    tail = text[-3000:]
+    assert r.returncode == 0, tail
+    m = re.search(r"^=* ?(\d+) passed, \d+ deselected[^\n]*$", text.strip().splitlines()[-1])
+    assert m and int(m.group(1)) == len(plantbins.CASES), tail
+    assert "skipped" not in text.strip().splitlines()[-1] and "xfailed" not in text.strip().splitlines()[-1], tail
+    assert f"Geometry({geometry}:" in text, tail
