@@ -5,6 +5,7 @@ import glob
 import hashlib
 import os
 import subprocess
+import sys
 import zlib
 
 import numpy as np
@@ -1200,3 +1201,84 @@ def test_planted_buckets_at_every_offset_of_the_detector_grid(ctx, case):
     assert t1["redo_groups"] == t0["redo_groups"] and c1["lsd"] == c0["lsd"] and c1["rank_count"] > c0["rank_count"], (t0, t1, c0, c1)
     g_n, g_rec = plantbins.n_giant(geo, planted)
     assert (c1["giant_tiles"] - c0["giant_tiles"], c1["giant_records"] - c0["giant_records"]) == (g_n, g_rec), (c0, c1, g_n, g_rec)
+
+
+# ------------------------------------------------------------------------------------------------ planted buckets of records of two words and more
+def _run_wide_case(ctx, case, env=os.environ):
+    """one case of plantbins.WIDE_CASES through ONE kmc_hip_process_bins_device call: per bin records, LUT and statistics against the oracle and against counts taken in numpy
+    from the ordered records the helper verified; the path counters exactly. Returns the outputs per bin."""
+    kind = capi.backend_kind()
+    geo = plantbins.geometry_of(kind, capi.lib_path())
+    c = plantbins.make_wide_case(geo, case, env)
+    wg, bins, planted, ordered = c.wg, c.bins, c.planted, c.ordered
+    print(f"planted-wide[{case}] {wg} k {c.k} groups (bins, rbits, passes, indirect) {c.groups}: {len(bins)} bins, {sum(len(pl) for pl in planted)} planted buckets, "
+          f"{sum(b[1] for b in bins)} records; k_giant_tiles passes over one bucket: {[plantbins.giant_passes(g[1]) for g in c.groups]}")
+    p = capi.make_params(c.k, **c.kw)
+    op_ = op(p)
+    rec = ctx.out_rec_bytes(p)
+    assert plantbins.plan_for(c.k, c.groups[0][0], 2 * wg.CAP, geo, 0 if p.without_output else rec, env) == c.groups[0][1:], "the record length the plan was made for"
+    t0, c0 = ctx.local_sort_totals(reset=False), ctx.path_counters()
+    got, err = _run_batch(ctx, p, bins, 1)
+    t1, c1 = ctx.local_sort_totals(reset=False), ctx.path_counters()
+    assert err is None, err
+    for i, (img, nrec, packs, _) in enumerate(bins):
+        w = O.process_bin(op_, img, nrec)
+        same = [np.array_equal(a, b) for a, b in zip(got[i], w)]
+        if not all(same):
+            d = _first_diff(got[i][0], w[0])
+            m = min(got[i][0].size, w[0].size)
+            j = int(np.flatnonzero(got[i][0][:m] != w[0][:m])[:1].sum()) // max(rec, 1)
+            where = plantbins.locate_wide(wg, planted[i], ordered[i], j, p.cutoff_min, p.cutoff_max)
+            dump = os.environ.get("KMC_PLANT_DUMP_DIR")
+            if dump:
+                np.savez(os.path.join(dump, f"planted_wide_{case}_bin{i}.npz"), image=img, got_out=got[i][0], want_out=w[0], got_lut=got[i][1], want_lut=w[1], got_stats=got[i][2],
+                         want_stats=w[2], planted=np.array([(f, L) for f, L, _ in planted[i]]), names=np.array([nm for _, _, nm in planted[i]]))
+            raise AssertionError(f"{case}: bin {i} of {len(bins)} differs from the oracle (records, LUT, statistics equal: {same}); statistics {got[i][2]} / {w[2]}; first "
+                                 f"difference {d}, output record {j}: {where}; redo {t1['redo_groups'] - t0['redo_groups']}")
+        # the second reference: counts taken here from the ordered records the helper verified on its own sort
+        distinct, below, above, n, counted = plantbins.independent_counts(ordered[i], p.cutoff_min, p.cutoff_max)
+        assert [int(x) for x in got[i][2]] == [distinct, below, above, n], (case, i, got[i][2], (distinct, below, above, n))
+        assert got[i][0].size == (0 if p.without_output else counted * rec), (case, i, got[i][0].size, counted, rec)
+        if ctx.lut_entries(p):
+            assert int(got[i][1].sum()) == (0 if p.without_output else counted), (case, i)
+    d = {x: c1[x] - c0[x] for x in c1}
+    g_n, g_rec, back = plantbins.n_giant_wide(wg, planted)
+    assert d["rank_count"] == len(c.groups) and d["rank_compact"] == 0 and d["bucket_count"] == 0, (d, c.groups)
+    assert d["lsd"] == len(back) and t1["redo_groups"] - t0["redo_groups"] == len(back), (d, t0, t1, back)
+    assert d["indirect"] == sum(1 for g in c.groups if g[3]), (d, c.groups)
+    assert (d["giant_tiles"], d["giant_records"]) == (g_n, g_rec), (d, g_n, g_rec)
+    if case.startswith("giant-run"):
+        assert plantbins.independent_counts(ordered[0], p.cutoff_min, p.cutoff_max)[2] == 1 and c.run > p.cutoff_max > c.second > p.counter_max, "the long run alone is dropped"
+    return got
+
+
+_WIDE_CHILD = ("import os, sys, numpy as np; sys.path.insert(0, 'tests'); from kmc_amd import capi; import test_gpu_parity as T; ctx = capi.Context((0,));"
+               "got = T._run_wide_case(ctx, 'w2-k55-indirect-off'); np.savez(sys.argv[1], **{f'{n}{i}': g[j] for i, g in enumerate(got) for j, n in enumerate(('out', 'lut', 'stats'))});"
+               "print('WIDE-CHILD-OK')")
+
+
+@pytest.mark.parametrize("case", plantbins.WIDE_CASES)
+def test_planted_buckets_of_wide_records(ctx, case, tmp_path):
+    """Records of two words and more take no arena: k_bucket_rank<2> ranks split (A, B) pairs, k_bucket_rank<3..> whole records through the br_rank_add_less borrow chain (inline
+    assembly on the device, a C++ twin under the emulation), the indirect sort gathers records by number, a bucket beyond a tile goes to k_giant_tiles, one beyond GT_MAX_RECORDS
+    sends its own bin back. tests/plantbins.py plants, in shuffled bins: buckets whose low bits differ in one dword only, across a borrow through equal / all-ones dwords, in
+    the bits around the A/B split, ties, extremes — each on a bucket its owners walk and on one dealt out over the workgroup (beyond BR_BIG); BR_BIG - 1 / BR_BIG / BR_BIG + 1
+    over a row seam, a wave seam and at the chunk cut; tiles of CAP and CAP + 1 records; buckets of CAP and CAP + 1 on a window's first and last record (giant with cut 0 and
+    cut S - 1); the first bucket start 0 .. 128 and thousands of records behind a window seam, windows without a start; k_giant_tiles around its chunk, an odd and an even
+    number of passes, a run over its chunk seams under cutoff_max / counter_max; GT_MAX and GT_MAX + 1 in the middle bin of three (one redo and one LSD run, no more: the
+    counters cannot tell that bin coming back alone from its group coming back once; every bin's output is compared either way). rbits 56 / 64 / 72 / 80
+    (the plan leaves whole bytes: 65 and 79 cannot occur), direct and indirect, k = 40 .. 256. Exact: records, LUT, statistics per bin equal the oracle's and numpy's counts;
+    rank_count, indirect, lsd, redo_groups and the giant counters equal what plantbins predicts."""
+    if case != "w2-k55-indirect-off":
+        _run_wide_case(ctx, case)
+        return
+    # the direct road on the bins of w2-k55, in a process of its own (KMC_HIP_INDIRECT is read once): the counters say the pairs were not used, the outputs equal the indirect road's
+    out = str(tmp_path / "direct.npz")
+    r = subprocess.run([sys.executable, "-c", _WIDE_CHILD, out], cwd=ROOT, env=dict(os.environ, KMC_HIP_INDIRECT="0"), capture_output=True, text=True, timeout=1200)
+    assert r.returncode == 0 and "WIDE-CHILD-OK" in r.stdout, (r.stdout + r.stderr)[-3000:]
+    print(r.stdout[-600:])
+    got = _run_wide_case(ctx, "w2-k55")
+    direct = np.load(out)
+    for i, g in enumerate(got):
+        for j, n in enumerate(("out", "lut", "stats")):
+            assert np.array_equal(direct[f"{n}{i}"], g[j]), (i, n)

@@ -300,3 +300,24 @@ def test_planted_bucket_sweep_on_the_emulated_host_library(geometry):
     assert m and int(m.group(1)) == len(plantbins.CASES), tail
     assert "skipped" not in text.strip().splitlines()[-1] and "xfailed" not in text.strip().splitlines()[-1], tail
     assert f"Geometry({geometry}:" in text, tail
+
+
+def test_planted_wide_sweep_on_the_emulated_host_library():
+    """test_planted_buckets_of_wide_records (test_gpu_parity.py, tests/plantbins.py WIDE_CASES) on the CPU, through the `small` emulated host library: CAP 512 / 256, GT_CHUNK
+    1024 / 512, GT_MAX 2048 — the same names at the lengths that geometry gives. `small_tight` differs from `small` only in BR_MID, which records of two words and more never
+    read (no arena): one geometry suffices. Every case must PASS in the child: a child that selects nothing, skips or fails a case fails here. (The emulation runs the C++
+    twin of br_rank_add_less; the borrow chain itself is checked by the same cases on the device.)"""
+    import plantbins
+
+    lib = emu.build_hostlib("small")
+    env = dict(os.environ, KMC_HIP_LIB=lib, KMC_PLANT_GEOMETRY="small")
+    env.pop("KMC_HIP_INDIRECT", None)
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-q", "-p", "no:cacheprovider", "-rA",
+                        "-k", "test_planted_buckets_of_wide_records"], env=env, capture_output=True, text=True, timeout=3000, cwd=ROOT)
+    text = r.stdout + r.stderr
+    tail = text[-3000:]
+    assert r.returncode == 0, tail
+    m = re.search(r"^=* ?(\d+) passed, \d+ deselected[^\n]*$", text.strip().splitlines()[-1])
+    assert m and int(m.group(1)) == len(plantbins.WIDE_CASES), tail
+    assert "skipped" not in text.strip().splitlines()[-1] and "xfailed" not in text.strip().splitlines()[-1], tail
+    assert "Geometry(small: SIZE=2 CAP=512 S=470 BIG=128 GT_CHUNK=1024 GT_MAX=2048)" in text and "Geometry(small: SIZE=4 CAP=256 S=235" in text, tail
