@@ -328,12 +328,19 @@ typedef struct kmc_hip_split_params {
 	uint32_t file_type;                              /* 0 = FASTA (one line per sequence), 1 = FASTQ, 2 = multi-line FASTA (-fm) */
 	uint64_t line_cap;                               /* CKMCParams::mem_part_pmm_reads */
 	uint32_t part_kind;                              /* 0 = whole records (ReadType::normal_read), 1 = ReadType::long_read */
-	uint32_t reserved;                               /* 0 */
+	uint32_t flags;                                  /* KMC_HIP_SPLIT_*; any other bit is KMC_HIP_EINVAL. (Named `reserved`, to be 0, before the first flag.) */
 } kmc_hip_split_params;
+/* flags bit 0: homopolymer compression (-hc). Every buffer CSplitter::GetSeq returns — a whole line, or ONE PIECE of a line of mem_part_pmm_reads symbols
+ * or more, of a long-read part or of a multi-line sequence — is compressed on its own before the super-k-mers are cut (HomopolymerCompressSeq,
+ * splitter.cpp:424-435, :575-581: the first symbol and every symbol whose code differs from the one before it), with every file_type and part_kind;
+ * *n_reads does not change. A library from before the flag ignores the field silently: ask kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_HOMOPOLYMER) first. */
+#define KMC_HIP_SPLIT_HOMOPOLYMER 1u
 int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, uint32_t signature_len);
 /* 1 if kmc_hip_split_part takes parts of this file_type, else 0. Added without a new ABI version: a loader that finds no such symbol takes file_type 0
- * and 1 only. */
-int kmc_hip_split_covers(uint32_t file_type);
+ * and 1 only. Values above the file types ask for a capability: KMC_HIP_SPLIT_COVERS_HOMOPOLYMER = the flag KMC_HIP_SPLIT_HOMOPOLYMER is honoured (a library
+ * from before the flag answers 0, like for every value it does not know). */
+#define KMC_HIP_SPLIT_COVERS_HOMOPOLYMER 0x100u
+int kmc_hip_split_covers(uint32_t what);
 int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint8_t *recs,
                        uint64_t recs_capacity, uint64_t *recs_bytes, uint64_t *bin_off, uint64_t *bin_bytes, uint64_t *bin_kmers, uint64_t *bin_superkmers, uint64_t *bin_plus_x,
                        uint64_t *n_reads);

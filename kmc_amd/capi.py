@@ -70,6 +70,17 @@ class BinDesc(C.Structure):
     ]
 
 
+class SplitParams(C.Structure):
+    """struct kmc_hip_split_params (one part of input text through stage 1, kmc_hip_split_part)."""
+
+    _fields_ = [("kmer_len", C.c_uint32), ("signature_len", C.c_uint32), ("n_bins", C.c_uint32), ("max_x", C.c_uint32), ("both_strands", C.c_uint32),
+                ("file_type", C.c_uint32), ("line_cap", C.c_uint64), ("part_kind", C.c_uint32), ("flags", C.c_uint32)]
+
+
+SPLIT_HOMOPOLYMER = 1  # KMC_HIP_SPLIT_HOMOPOLYMER: flags bit 0, -hc
+SPLIT_COVERS_HOMOPOLYMER = 0x100  # KMC_HIP_SPLIT_COVERS_HOMOPOLYMER: ask kmc_hip_split_covers before setting the flag (an older library ignores it)
+
+
 def make_params(k, both_strands=1, cutoff_min=2, cutoff_max=10**9, counter_max=255, lut_prefix_len=3, output_type=0,
                 without_output=0) -> BinParams:
     return BinParams(k, both_strands, cutoff_min, without_output, cutoff_max, counter_max, lut_prefix_len, output_type)
@@ -167,7 +178,7 @@ def load():
     L.kmc_hip_debug_expand.argtypes = [vp, C.c_int, C.POINTER(BinParams), vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp]
     L.kmc_hip_debug_compact.argtypes = [vp, C.c_int, C.POINTER(BinParams), vp, C.c_uint64, vp, C.c_uint64, u64p, vp, u64p]
     L.kmc_hip_debug_split_reads.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, u64p]
-    if hasattr(L, "kmc_hip_split_covers"):  # added within ABI version 4: a library without it takes file_type 0 and 1 only
+    if hasattr(L, "kmc_hip_split_covers"):  # added within ABI version 4: a library without it takes file_type 0 and 1 only, and no flags
         L.kmc_hip_split_covers.argtypes = [C.c_uint32]
     _LIB = L
     return L

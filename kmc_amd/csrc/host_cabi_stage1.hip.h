@@ -347,7 +347,7 @@ int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, 
 	return 0;
 }
 
-int kmc_hip_split_covers(uint32_t file_type) { return file_type <= 2 ? 1 : 0; }
+int kmc_hip_split_covers(uint32_t what) { return what <= 2 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER ? 1 : 0; }
 
 int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint8_t *recs,
                        uint64_t recs_capacity, uint64_t *recs_bytes, uint64_t *bin_off, uint64_t *bin_bytes, uint64_t *bin_kmers, uint64_t *bin_superkmers, uint64_t *bin_plus_x,
@@ -360,6 +360,8 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 	if (p->kmer_len < 1 || p->kmer_len > (uint32_t)S1_MAX_K || p->signature_len < 5 || p->signature_len > 11 || p->signature_len > p->kmer_len || p->n_bins < 1 ||
 	    p->n_bins > (uint32_t)S1_MAX_BINS || p->max_x > 3 || p->file_type > 2 || p->part_kind > 1 || (p->max_x && p->kmer_len < 4))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: unsupported parameters");
+	if (p->flags & ~KMC_HIP_SPLIT_HOMOPOLYMER)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: unknown bit in flags");
 	if (p->file_type == 2 && p->part_kind != 0)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: a multi-line FASTA part (file_type 2) is a ReadType::na part: part_kind must be 0");
 	/* a configuration limit, not a property of the text: the pieces of an over-long line are cut at workgroup windows (stage1_chain.h) */
@@ -373,8 +375,10 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 	Slot &s = d.slot[slot];
 	std::lock_guard<std::mutex> lck(s.mtx);
 	/* text + codes + line ends (2 B per byte of text at most, see stage1_chain.h; multi-line FASTA: sequence starts, 4 B per byte) + super-k-mers
-	 * (2 B per symbol at the first guess) + records (~0.3 B per symbol) + per-bin arrays */
-	if (int rc = ensure(d.s1_arena[slot], (size_t)size * (p->file_type == 2 ? 10 : 8) + ((size_t)32 << 20)))
+	 * (2 B per symbol at the first guess) + records (~0.3 B per symbol) + per-bin arrays; -hc: the compacted code stream (1 B per symbol + k per piece
+	 * start, which are more than 4096 symbols apart: under 2 B per byte of text with its look-back words) */
+	const bool hc = (p->flags & KMC_HIP_SPLIT_HOMOPOLYMER) != 0;
+	if (int rc = ensure(d.s1_arena[slot], (size_t)size * ((p->file_type == 2 ? 10 : 8) + (hc ? 2 : 0)) + ((size_t)32 << 20)))
 		return rc;
 	S1HipBackend be;
 	be.stream = s.stream;
@@ -388,6 +392,7 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 	sp.both_strands = p->both_strands ? 1u : 0u;
 	sp.lines_per_record = p->file_type == 1 ? 4u : 2u;
 	sp.multiline_fasta = p->file_type == 2;
+	sp.homopolymer = hc;
 	sp.line_cap = p->line_cap;
 	sp.d_sig_to_bin = d.d_sig_map;
 	sp.sorted_emit = getenv("KMC_HIP_S1_SORTED_EMIT") != nullptr; /* the alternative emit (stage1_kernels.hip.h): to be measured before it becomes the default */

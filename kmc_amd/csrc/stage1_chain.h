@@ -33,6 +33,8 @@ struct S1PartParams {
 	bool sorted_emit = false;                                 /* records through a sort by bin (k_s1_emit_sorted) instead of k_s1_emit: bins in read order */
 	bool multiline_fasta = false;                             /* a multi-line FASTA part (ReadType::na, GetSeq splitter.cpp:304-323): k_s1_ml_text_to_codes;
 	                                                           * lines_per_record is not used */
+	bool homopolymer = false;                                 /* -hc: every return of GetSeq — a line, or one PIECE of an over-long line / a long-read part — is
+	                                                           * homopolymer-compressed on its own (splitter.cpp:424-435, :575-581): k_s1_hc_compact in front of the cut */
 };
 struct S1PartResult {
 	const uint8_t *d_recs = nullptr; /* device: bin b's records at d_recs + bin_off[b], bin_bytes[b] of them */
@@ -69,7 +71,8 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 	R.bin_plus_x.assign(nb, 0);
 	if (!size)
 		return S1_CHAIN_OK;
-	/* small block: [0] '\\n' count | [1] code bytes | [2] super-k-mers | [3] lo: ticket, hi: error word | [4] != 0: some code carries S1_PIECE_MARK */
+	/* small block: [0] '\\n' count | [1] code bytes | [2] super-k-mers | [3] lo: ticket, hi: error word | [4] != 0: some code carries S1_PIECE_MARK |
+	 * [5] code bytes after k_s1_hc_compact */
 	u64 *d_small = (u64 *)be.alloc(64);
 	u32 *d_ticket = (u32 *)(d_small + 3), *d_err = d_ticket + 1;
 	u64 *d_has_marks = d_small + 4;
@@ -134,6 +137,29 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 		} else if (n > stride) /* n_reads of a long-read part: the caller knows whether it took a title off */
 			S1_LAUNCH(B, be, k_s1_mark_raw, dim3(1), dim3(256), d_codes, n, stride, d_has_marks);
 	}
+	/* ---- -hc: the compacted stream (pieces have become sequences of their own: no marks) replaces the code stream for everything below */
+	const u64 *d_cut_marks = d_has_marks;
+	if (P.homopolymer && n) {
+		const u64 hc_cap = n + (n / stride + 1) * P.k; /* a mark adds its k - 1 tail codes and a separator; marks are `stride` apart */
+		const u32 ht = (u32)((n + S1_TXT_TILE - 1) / S1_TXT_TILE);
+		int8_t *d_hc = (int8_t *)be.alloc_uninit(hc_cap + 16);
+		u64 *d_hstat = (u64 *)be.alloc((size_t)ht * 8);
+		be.zero(d_ticket, 4);
+		S1_LAUNCH(B, be, k_s1_hc_compact, dim3(ht), dim3(S1_BLOCK), (const int8_t *)d_codes, n, P.k, d_hstat, d_ticket, d_hc, hc_cap, d_small + 5, d_err);
+		u64 hc[3]; /* ticket, error word | has_marks | compacted codes */
+		if (!be.d2h(hc, d_small + 3, sizeof hc))
+			return S1_CHAIN_BACKEND_FAILURE;
+		err = (u32)(hc[0] >> 32);
+		if (err & S1_TEXT_BAD)
+			return S1_CHAIN_UNCOVERED; /* the record check ran beside the compaction */
+		if (err) {
+			R.device_error = err;
+			return S1_CHAIN_DEVICE_ERROR;
+		}
+		d_codes = d_hc;
+		n = hc[2];
+		d_cut_marks = nullptr;
+	}
 	/* ---- codes -> super-k-mers. Their number is only known afterwards: a guess, and a second cut with the exact number when it was short. */
 	u64 n_sk = 0, cap = n / P.sk_guess_div + 4096;
 	u64 *d_pos = nullptr;
@@ -151,7 +177,7 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 			}
 			be.zero(d_ticket, 4);
 			S1_LAUNCH(B, be, (k_s1_cut<true>), dim3(ct), dim3(S1_BLOCK), (const u32 *)nullptr, (const int8_t *)d_codes, P.m, n, P.k, d_cstat, d_cstat + ct, d_ticket, d_pos,
-			          d_len, d_sig, cap, d_small + 2, (const u64 *)d_has_marks, d_err);
+			          d_len, d_sig, cap, d_small + 2, d_cut_marks, d_err);
 			if (!be.d2h(small, d_small, sizeof small))
 				return S1_CHAIN_BACKEND_FAILURE;
 			err = (u32)(small[3] >> 32);

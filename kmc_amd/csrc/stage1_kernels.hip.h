@@ -879,6 +879,153 @@ __global__ void __launch_bounds__(256) k_s1_ml_marks(const uint8_t *__restrict__
 	}
 }
 
+/* ------------------------------------------------------------------------------------------------ homopolymer compression (-hc)
+ * CSplitter::ProcessReads calls HomopolymerCompressSeq (splitter.cpp:424-435, :575-581) on every buffer GetSeq returns, before the super-k-mer loop: the
+ * first symbol stays, and every symbol whose CODE differs from the one before it ("aAaA" is one symbol, every invalid symbol is the same -1). A return of
+ * GetSeq is a whole line, or ONE PIECE of a line of line_cap symbols or more / of a long-read part / of a multi-line sequence: pieces are compressed one
+ * by one, so the k - 1 raw symbols two neighbours share are compressed twice, and a piece keeps its first symbol whatever stood in front of it. This is not
+ * "compress the line, then cut": a run across a piece start, or inside the overlap, changes which k-mers exist.
+ *
+ * k_s1_hc_compact: the code stream (codes 0..3 or negative, sequences joined by a negative separator, piece starts carrying S1_PIECE_MARK) -> the stream
+ * of the compressed returns, in which PIECES ARE SEQUENCES: no code carries the mark (k_s1_cut runs without has_marks), and a marked position M becomes
+ *     ... main codes before M | codes of [M, M + k - 1) once more, as the tail of the piece that ends there (compared with the code in front, M - 1
+ *     included) | one separator (-1) | main codes from M on, the one at M kept unconditionally.
+ * The tail is taken as it stands up to M + k - 1 or the end of the stream; where the line ends earlier the surplus is fewer than k symbols in front of a
+ * separator and makes no k-mer. A mark that fell on an invalid code was never set (the markers skip negative codes): harmless, because an invalid symbol at a
+ * piece start leaves fewer than k symbols of the duplicated tail behind it, and the symbol after it starts a run anyway. Runs of invalid codes ARE
+ * compressed (N runs and the separator next to them become one -1): the k-mers, super-k-mers and sums do not depend on it, and it keeps one rule for all codes.
+ * Marks are more than S1_TXT_TILE positions apart (stride > S1_WG_TILE, stage1_chain.h), so a tile holds at most one, and the tile that holds the mark
+ * emits the whole tail (up to k - 1 <= 255 codes, read again from memory: they may lie in the next tile). One decoupled look-back over kept codes + tail +
+ * separator gives the tile's output offset; the tile's output is put together in LDS and leaves in 16-byte stores. status: one zeroed u64 per tile.
+ * *n_out = codes written (<= n + marks * k; out_cap bounds the stores, KERR_CAPACITY beyond it). */
+constexpr u32 S1_HC_NONE = 0xFFFFFFFFu;
+__device__ __forceinline__ u32 s1_hc_key(int8_t c) { return c < 0 ? 4u : (u32)(c & 3); }
+
+__global__ void __launch_bounds__(S1_BLOCK) k_s1_hc_compact(const int8_t *__restrict__ codes, u64 n, u32 k, u64 *status, u32 *ticket_ctr, int8_t *__restrict__ out,
+                                                             u64 out_cap, u64 *n_out, u32 *err)
+{
+	__shared__ __attribute__((aligned(16))) int8_t s_out[S1_TXT_TILE + S1_MAX_K + 32]; /* 15 bytes of alignment + the tile's codes + tail + separator */
+	__shared__ u32 s_tmp[S1_BLOCK / 64 + 1];
+	__shared__ u64 s_carry;
+	__shared__ u32 s_ticket, s_mark, s_mark_rank;
+	const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	if (tid == 0) {
+		s_ticket = atomicAdd(ticket_ctr, 1u);
+		s_mark = S1_HC_NONE;
+	}
+	__syncthreads();
+	const u32 tile = s_ticket;
+	const u32 num_tiles = (u32)((n + S1_TXT_TILE - 1) / S1_TXT_TILE);
+	if (tile >= num_tiles)
+		return;
+	const u64 tile0 = (u64)tile * S1_TXT_TILE, p0 = tile0 + (u64)tid * S1_TXT_PER;
+	int8_t c[S1_TXT_PER];
+	static_assert(S1_TXT_PER == 16, "one 16-byte load per thread");
+	if (p0 + S1_TXT_PER <= n) {
+		u32 w[4];
+		__builtin_memcpy(w, codes + p0, 16);
+#pragma unroll
+		for (int j = 0; j < S1_TXT_PER; ++j)
+			c[j] = (int8_t)(w[j >> 2] >> (8 * (j & 3)));
+	} else {
+#pragma unroll
+		for (int j = 0; j < S1_TXT_PER; ++j)
+			c[j] = p0 + j < n ? codes[p0 + j] : (int8_t)-1;
+	}
+	/* ---- main role: the code differs from the one in front, or is the first of the stream, or starts a piece */
+	u32 prev = p0 > 0 && p0 < n ? s1_hc_key(codes[p0 - 1]) : 5u; /* 5: nothing in front */
+	u32 keep = 0, my_mark = S1_HC_NONE;
+#pragma unroll
+	for (int j = 0; j < S1_TXT_PER; ++j) {
+		if (p0 + j >= n)
+			break;
+		const u32 key = s1_hc_key(c[j]);
+		const bool marked = (c[j] & 0xC0) == S1_PIECE_MARK;
+		if (key != prev || marked)
+			keep |= 1u << j;
+		if (marked)
+			my_mark = (u32)j;
+		prev = key;
+	}
+	u32 tile_keep;
+	const u32 keep_before = block_excl_sum<S1_BLOCK / 64, u32>((u32)__popc(keep), s_tmp, tile_keep);
+	if (my_mark != S1_HC_NONE) { /* one thread of the tile at most */
+		s_mark = tid * S1_TXT_PER + my_mark;
+		s_mark_rank = keep_before + (u32)__popc(keep & ((1u << my_mark) - 1u));
+	}
+	__syncthreads();
+	/* ---- tail role (rare, tile-uniform): thread t takes position M + t of [M, M + k - 1); ranks from the waves' ballots */
+	const u32 mk = s_mark;
+	u32 tail_cnt = 0, tail_rank = 0, extra = 0;
+	bool tail_keep = false;
+	int8_t tail_code = -1;
+	if (mk != S1_HC_NONE) {
+		const u64 q = tile0 + mk + tid;
+		if (tid + 1 < k && q < n) {
+			const int8_t a = codes[q];
+			tail_keep = s1_hc_key(a) != (q > 0 ? s1_hc_key(codes[q - 1]) : 5u);
+			tail_code = a < 0 ? (int8_t)-1 : (int8_t)(a & 3);
+		}
+		const u64 bal = __ballot(tail_keep);
+		const u32 below = __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
+		if (lane == 0)
+			s_tmp[wave] = (u32)__popcll(bal);
+		__syncthreads();
+#pragma unroll
+		for (u32 i = 0; i < (u32)S1_BLOCK / 64; ++i) {
+			tail_rank += i < wave ? s_tmp[i] : 0u;
+			tail_cnt += s_tmp[i];
+		}
+		tail_rank += below;
+		extra = tail_cnt + 1; /* + the separator */
+	}
+	const u32 tile_out = tile_keep + extra;
+	if (wave == 0) {
+		const u64 excl = lookback64(status, tile, (u64)tile_out, lane, err, KERR_WATCHDOG | KERR_AT_STAGE1);
+		if (lane == 0) {
+			s_carry = excl;
+			if (tile == num_tiles - 1)
+				*n_out = excl + tile_out;
+		}
+	}
+	__syncthreads();
+	const u64 at0 = s_carry;
+	if (at0 + tile_out > out_cap) { /* tile-uniform; cannot happen with the chain's sizing */
+		if (tid == 0)
+			atomicOr(err, KERR_CAPACITY);
+		return;
+	}
+	/* ---- the tile's output in LDS, shifted by the misalignment of its place in `out`: 16-byte chunks of s_out are 16-byte chunks of `out` */
+	const u32 mis = (u32)((uintptr_t)(out + at0) & 15u);
+	u32 idx = mis + keep_before + (tid * S1_TXT_PER > mk && mk != S1_HC_NONE ? extra : 0u);
+#pragma unroll
+	for (int j = 0; j < S1_TXT_PER; ++j) {
+		if (tid * S1_TXT_PER + (u32)j == mk)
+			idx += extra; /* the tail and its separator go in front of the marked code */
+		if (keep & (1u << j))
+			s_out[idx++] = c[j] < 0 ? (int8_t)-1 : (int8_t)(c[j] & 3);
+	}
+	if (mk != S1_HC_NONE) {
+		if (tail_keep)
+			s_out[mis + s_mark_rank + tail_rank] = tail_code;
+		if (tid == 0)
+			s_out[mis + s_mark_rank + tail_cnt] = (int8_t)-1;
+	}
+	__syncthreads();
+	int8_t *dst = out + at0 - mis; /* 16-byte aligned */
+	const u32 lo_valid = mis, hi_valid = mis + tile_out;
+	for (u32 ch = tid; ch * 16u < hi_valid; ch += S1_BLOCK) {
+		const u32 lo = ch * 16u;
+		if (lo >= lo_valid && lo + 16u <= hi_valid) {
+			uint4 v;
+			__builtin_memcpy(&v, __builtin_assume_aligned(s_out + lo, 16), 16);
+			__builtin_memcpy(__builtin_assume_aligned(dst + lo, 16), &v, 16);
+		} else
+			for (u32 i = lo > lo_valid ? lo : lo_valid; i < lo + 16u && i < hi_valid; ++i)
+				dst[i] = s_out[i];
+	}
+}
+
 /* n_plus_x_recs per bin: how many (k+x)-mer records the reference's stage 2 expands each super-k-mer into (kb_collector.cpp:83-100,
  * kb_collector.h:72-118) — the third sum a CKmerBinCollector keeps, which stage 2 sizes its arrays with. One thread per super-k-mer walks
  * its k-mers comparing the first four symbols of the k-mer with those of its reverse complement. */

@@ -22,7 +22,7 @@ struct SplitApi {
 	int (*split_part)(kmc_hip_ctx *, int, int, const kmc_hip_split_params *, const uint8_t *, uint64_t, uint8_t *, uint64_t, uint64_t *, uint64_t *, uint64_t *,
 	                  uint64_t *, uint64_t *, uint64_t *, uint64_t *) = nullptr;
 	const char *(*last_error)(kmc_hip_ctx *) = nullptr;
-	int (*covers)(uint32_t) = nullptr; /* optional: a library without kmc_hip_split_covers takes FASTA and FASTQ only */
+	int (*covers)(uint32_t) = nullptr; /* optional: a library without kmc_hip_split_covers takes FASTA and FASTQ only, and no flags */
 	kmc_hip_ctx *ctx = nullptr;
 	int n_dev = 1, n_slots = 1;
 	std::string err;
@@ -66,6 +66,8 @@ struct HipSplitEngine : KmcSplitEngine {
 	}
 	std::string last_error() override { return err; }
 	bool covers_multiline_fasta() const override { return g_split.ctx && g_split.covers && g_split.covers(2) == 1; }
+	/* a library from before the flag ignores it silently: the query is the only way to know */
+	bool covers_homopolymer_compression() const override { return g_split.ctx && g_split.covers && g_split.covers(KMC_HIP_SPLIT_COVERS_HOMOPOLYMER) == 1; }
 	int split_part(const uint8_t *text, uint64_t size, bool long_read, KmcSplitResult &out) override
 	{
 		if (!g_split.ctx) {
@@ -91,7 +93,7 @@ struct HipSplitEngine : KmcSplitEngine {
 		hp.file_type = (uint32_t)P.file_type;
 		hp.line_cap = P.line_cap;
 		hp.part_kind = long_read ? 1u : 0u;
-		hp.reserved = 0;
+		hp.flags = P.homopolymer_compressed ? KMC_HIP_SPLIT_HOMOPOLYMER : 0u;
 		/* records of real reads take ~0.3 bytes per symbol; text whose k-mers are nearly all their own super-k-mer needs more: second call */
 		if (recs.size() < size + 256ull * (P.n_bins + 1))
 			recs.resize(size + 256ull * (P.n_bins + 1));

@@ -21,12 +21,14 @@
  *
  * FAILS CLOSED (round 5): this worker has no path into the reference's CSplitter. What the engine does not cover stops the run through
  * CCriticalErrorHandler with a message that names it —
- *   per job : input other than FASTA / FASTQ (BAM, KMC; multi-line FASTA unless the engine covers_multiline_fasta()), homopolymer compression (-hc), histogram estimation while counting (--opt-out-size; -e alone runs the reference's estimate-only worker, not this one):
+ *   per job : input other than FASTA / FASTQ (BAM, KMC; multi-line FASTA unless the engine covers_multiline_fasta()), homopolymer compression (-hc) unless the engine covers_homopolymer_compression(), histogram estimation while counting (--opt-out-size; -e alone runs the reference's estimate-only worker, not this one):
  *             "use kmc_hip" (the reference's stage 1 + this library's stage 2) is the answer the message gives;
  *   per part: KMC_SPLIT_UNCOVERED — MALFORMED text that CSplitter::GetSeq happens to tolerate (blank lines, a quality string of another length than its
  *             sequence, control characters, a lone '\r').
  * Parts the reader labelled ReadType::long_read (queues.h:40) and lines of mem_part_pmm_reads symbols or more go through the engine like any other, and so
- * do the ReadType::na parts of multi-line FASTA (fastq_reader.cpp:399-468, :579-583) with an engine that covers them (file_type 2).
+ * do the ReadType::na parts of multi-line FASTA (fastq_reader.cpp:399-468, :579-583) with an engine that covers them (file_type 2). With -hc the engine
+ * compresses every return of GetSeq on its own, as ProcessReads does (splitter.cpp:575-581); stage 0, the small-k worker and the estimate worker stay the
+ * reference's and honour the flag themselves, and n_reads does not depend on it.
  * Only a build with -DKMC_HIP_S1_REFERENCE_FALLBACK (no shipped binary has it; oracle/_ref/kmc_emu_s1_fb is the test build) AND $KMC_HIP_S1_FALLBACK=1
  * in the environment hands such jobs / parts to the reference (CWSplitter_ref / a CSplitter of this thread, our buffers pushed first) and says so on stderr;
  * nothing run that way is covered by this repo's parity claims.
@@ -110,11 +112,11 @@ class CWSplitter {
 	uint64 st_parts = 0, st_long_parts = 0, st_ml_parts = 0, st_uncovered_parts = 0, st_pieces = 0, st_cut_pieces = 0, st_pushes = 0, st_bytes = 0;
 	long long st_engine_ns = 0;
 
-	static const char *uncovered_job(const CKMCParams &P, bool multiline_covered)
+	static const char *uncovered_job(const CKMCParams &P, bool multiline_covered, bool homopolymer_covered)
 	{
 		if (P.file_type != InputType::FASTA && P.file_type != InputType::FASTQ && !(P.file_type == InputType::MULTILINE_FASTA && multiline_covered))
 			return "an input format other than FASTA / FASTQ (multi-line FASTA, BAM, KMC)";
-		if (P.homopolymer_compressed)
+		if (P.homopolymer_compressed && !homopolymer_covered)
 			return "homopolymer compression (-hc)";
 		if (P.estimateHistogramCfg == KMC::EstimateHistogramCfg::ESTIMATE_AND_COUNT_KMERS)
 			return "histogram estimation while counting (--opt-out-size)";
@@ -204,6 +206,7 @@ class CWSplitter {
 		sp.file_type = Params.file_type == InputType::FASTQ ? 1 : Params.file_type == InputType::MULTILINE_FASTA ? 2 : 0;
 		sp.line_cap = (uint64_t)Params.mem_part_pmm_reads;
 		sp.sig_to_bin = Queues.s_mapper->GetMap();
+		sp.homopolymer_compressed = Params.homopolymer_compressed ? 1 : 0;
 		static std::atomic<int> next_idx{0};
 		return kmc_make_split_engine(sp, next_idx++ % (int)Params.n_splitters, (int)Params.n_splitters);
 	}
@@ -222,9 +225,9 @@ public:
 		max_x = Params.max_x;
 		both_strands = Params.both_strands;
 		buffer_size = Params.bin_part_size;
-		if (Params.file_type == InputType::MULTILINE_FASTA)
-			engine.reset(make_engine(Params, Queues)); /* whether the format is covered is the engine's answer */
-		if (const char *what = uncovered_job(Params, engine && engine->covers_multiline_fasta())) {
+		if (Params.file_type == InputType::MULTILINE_FASTA || Params.homopolymer_compressed)
+			engine.reset(make_engine(Params, Queues)); /* whether the format / the compression is covered is the engine's answer */
+		if (const char *what = uncovered_job(Params, engine && engine->covers_multiline_fasta(), engine && engine->covers_homopolymer_compression())) {
 #ifdef KMC_HIP_S1_REFERENCE_FALLBACK
 			const char *fb = getenv("KMC_HIP_S1_FALLBACK");
 			if (fb && fb[0] == '1') {
@@ -315,10 +318,11 @@ public:
 		KmcTimeline::mark_first_last(nullptr, "splitter: last worker done");
 		if (getenv("KMC_HIP_VERBOSE"))
 			fprintf(stderr, "[kmc_hip stage 1] worker: %llu parts through the engine (%.3f s inside; %llu of them long-read parts), %llu uncovered parts, "
-			                "%llu bin pieces (%llu cut record by record), %llu buffers / %.1f MB pushed, %llu multi-line FASTA parts\n",
+			                "%llu bin pieces (%llu cut record by record), %llu buffers / %.1f MB pushed, %llu multi-line FASTA parts%s\n",
 			        (unsigned long long)st_parts, st_engine_ns * 1e-9, (unsigned long long)st_long_parts, (unsigned long long)st_uncovered_parts,
 			        (unsigned long long)st_pieces,
-			        (unsigned long long)st_cut_pieces, (unsigned long long)st_pushes, st_bytes / 1e6, (unsigned long long)st_ml_parts);
+			        (unsigned long long)st_cut_pieces, (unsigned long long)st_pushes, st_bytes / 1e6, (unsigned long long)st_ml_parts,
+			        params->homopolymer_compressed ? ", homopolymer-compressed (-hc) on the device" : "");
 	}
 
 	void GetTotal(uint64 &_n_reads)

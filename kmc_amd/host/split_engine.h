@@ -23,6 +23,8 @@ struct KmcSplitParams {
 	int file_type;             /* 0 = FASTA (one line per sequence), 1 = FASTQ, 2 = multi-line FASTA (ReadType::na parts; only for an engine that covers_multiline_fasta()) */
 	uint64_t line_cap;         /* mem_part_pmm_reads: longer lines are cut into pieces overlapping by kmer_len - 1 symbols (splitter.cpp:141-145) */
 	const int32_t *sig_to_bin; /* CSignatureMapper's map, 4^signature_len + 1 entries (s_mapper.h:232) */
+	int homopolymer_compressed = 0; /* -hc: every return of GetSeq is compressed on its own (splitter.cpp:424-435, :575-581); only for an engine that
+	                                 * covers_homopolymer_compression() */
 };
 
 /* valid until the next split_part() on the same engine */
@@ -45,6 +47,8 @@ struct KmcSplitEngine {
 	virtual std::string last_error() = 0;
 	/* parts of multi-line FASTA (file_type 2: CFastqReader::GetPartFromMultilneFasta, split as CSplitter::GetSeq's MULTILINE_FASTA branch) */
 	virtual bool covers_multiline_fasta() const { return false; }
+	/* -hc (KmcSplitParams::homopolymer_compressed), with every file type and with long-read parts */
+	virtual bool covers_homopolymer_compression() const { return false; }
 };
 
 /* Provided by exactly one engine implementation linked into the binary. */

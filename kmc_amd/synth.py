@@ -118,6 +118,43 @@ def make_multiline_fasta(path: str, seed: int, contig_lens, line_width: int = 60
     return total
 
 
+def homopolymer_rich_sequence(rng, n: int, mean_run: float = 2.0, lower_frac: float = 0.0, n_run_per_mbp: float = 0.0, n_run_len: int = 50) -> np.ndarray:
+    """`n` ASCII symbols whose homopolymer runs have geometric lengths of mean `mean_run` (successive runs differ in their symbol), a share
+    `lower_frac` of the SYMBOLS in lower case (symbol by symbol, so that a run mixes cases: "aAaA" is one homopolymer to -hc), and
+    `n_run_per_mbp` runs of `n_run_len` N per Mbp."""
+    if n <= 0:
+        return np.zeros(0, dtype=np.uint8)
+    n_runs = int(n / mean_run * 1.2) + 16
+    while True:
+        lens = rng.geometric(1.0 / mean_run, size=n_runs)
+        if int(lens.sum()) >= n:
+            break
+        n_runs *= 2
+    sym = np.cumsum(rng.integers(1, 4, size=n_runs)) & 3  # never the symbol of the run before
+    seq = _ACGT[np.repeat(sym, lens)[:n]].copy()
+    if lower_frac > 0:
+        seq = np.where(rng.random(n) < lower_frac, seq | 0x20, seq).astype(np.uint8)
+    if n_run_per_mbp > 0:
+        for s0 in rng.integers(0, n, size=int(rng.poisson(n_run_per_mbp * n / 1e6))):
+            seq[s0:s0 + n_run_len] = ord("N")
+    return seq
+
+
+def make_long_reads(path: str, seed: int, read_lens, fmt: str = "fq", mean_run: float = 2.0, lower_frac: float = 0.1, n_run_per_mbp: float = 20.0,
+                    n_run_len: int = 50, eol: bytes = b"\n") -> int:
+    """Write homopolymer-rich long reads (the input -hc is meant for: ONT / PacBio): one record per length in `read_lens`, the sequence on ONE
+    line, as FASTQ (`fmt` "fq": constant quality 'I') or FASTA ("fa"). Sequences come from homopolymer_rich_sequence. Returns bytes written."""
+    rng = np.random.default_rng(seed)
+    total = 0
+    with open(path, "wb") as f:
+        for i, n in enumerate(int(x) for x in read_lens):
+            seq = homopolymer_rich_sequence(rng, n, mean_run, lower_frac, n_run_per_mbp, n_run_len).tobytes()
+            rec = (b"@read_%d len=%d" % (i, n) + eol + seq + eol + b"+" + eol + b"I" * n + eol) if fmt == "fq" else (b">read_%d len=%d" % (i, n) + eol + seq + eol)
+            f.write(rec)
+            total += len(rec)
+    return total
+
+
 # Named configurations of BASELINE.json / SURVEY.md §8d
 CONFIGS = {
     "C1": dict(seed=12345, genome_len=400_000, n_reads=33_000),          # 10 MB FASTQ plumbing case
