@@ -335,15 +335,37 @@ typedef struct kmc_hip_split_params {
  * splitter.cpp:424-435, :575-581: the first symbol and every symbol whose code differs from the one before it), with every file_type and part_kind;
  * *n_reads does not change. A library from before the flag ignores the field silently: ask kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_HOMOPOLYMER) first. */
 #define KMC_HIP_SPLIT_HOMOPOLYMER 1u
+/* flags bit 2 (value 4; value 2 stays an unknown bit): histogram estimation while counting (--opt-out-size). The k-mers of the part — of every buffer
+ * CSplitter::GetSeq returns, BEFORE the homopolymer compression, as CntHashEstimator::Process sees them (splitter.cpp:576-577) — are added to the estimator
+ * that kmc_hip_estimate_open opened on `dev`; KMC_HIP_EINVAL when none is open or its kmer_len differs. Works with every file_type, part_kind and with
+ * KMC_HIP_SPLIT_HOMOPOLYMER. A call that does not return 0 (KMC_HIP_UNCOVERED and KMC_HIP_ECAPACITY included) leaves the counters as they were. Ask
+ * kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_ESTIMATE) first. */
+#define KMC_HIP_SPLIT_ESTIMATE 4u
 int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, uint32_t signature_len);
 /* 1 if kmc_hip_split_part takes parts of this file_type, else 0. Added without a new ABI version: a loader that finds no such symbol takes file_type 0
  * and 1 only. Values above the file types ask for a capability: KMC_HIP_SPLIT_COVERS_HOMOPOLYMER = the flag KMC_HIP_SPLIT_HOMOPOLYMER is honoured (a library
  * from before the flag answers 0, like for every value it does not know). */
 #define KMC_HIP_SPLIT_COVERS_HOMOPOLYMER 0x100u
+#define KMC_HIP_SPLIT_COVERS_ESTIMATE 0x102u /* KMC_HIP_SPLIT_ESTIMATE and kmc_hip_estimate_open / _read / _close (0x101 stays unknown) */
 int kmc_hip_split_covers(uint32_t what);
 int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint8_t *recs,
                        uint64_t recs_capacity, uint64_t *recs_bytes, uint64_t *bin_off, uint64_t *bin_bytes, uint64_t *bin_kmers, uint64_t *bin_superkmers, uint64_t *bin_plus_x,
                        uint64_t *n_reads);
+
+/* ---- stage 1, histogram estimation while counting (--opt-out-size; added within ABI version 4, like kmc_hip_split_covers) ----
+ * The device's share of the reference's CntHashEstimator (kmc_core/libs/ntHash/ntHashWrapper.h): two arrays of 2^r 32-bit counters on `dev`, to which every
+ * kmc_hip_split_part call with KMC_HIP_SPLIT_ESTIMATE adds the sampled ntHash values of its part's k-mers (k_s1_nthash_estimate; counters wrap at 2^32 like
+ * the reference's). The caller adds the counters of all devices into the reference's own object, whose EstimateHistogram then runs unchanged.
+ * _open : allocates and zeroes 2 x 2^r counters (1 GB at the reference's r = 27); s in 1..16, r in 8..27 (the reference: s = 7 or 11). Opening again with the
+ *         same (kmer_len, s, r) is a no-op, with another triple KMC_HIP_EINVAL.
+ * _read : waits for everything the device's slots have launched, then copies entries [first, first + count) of the 2^(r+1)-entry array (type 0 first, then
+ *         type 1) to dst: a caller can drain in chunks, without a second gigabyte on the host. The counters are not cleared.
+ * _close: frees the counters (kmc_hip_destroy does it too); no estimator open is not an error. It waits for the kmc_hip_split_part calls with
+ * KMC_HIP_SPLIT_ESTIMATE that are inside the library on `dev`; a call that starts after it finds no estimator (KMC_HIP_EINVAL). kmc_hip_destroy does not
+ * wait: like every other call, none may be running when it is called. */
+int kmc_hip_estimate_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t s, uint32_t r);
+int kmc_hip_estimate_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint32_t *dst);
+int kmc_hip_estimate_close(kmc_hip_ctx *ctx, int dev);
 
 #ifdef __cplusplus
 }

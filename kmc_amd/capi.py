@@ -78,6 +78,8 @@ class SplitParams(C.Structure):
 
 
 SPLIT_HOMOPOLYMER = 1  # KMC_HIP_SPLIT_HOMOPOLYMER: flags bit 0, -hc
+SPLIT_ESTIMATE = 4  # KMC_HIP_SPLIT_ESTIMATE: flags bit 2, --opt-out-size (the part's k-mers go to the estimator of kmc_hip_estimate_open)
+SPLIT_COVERS_ESTIMATE = 0x102  # KMC_HIP_SPLIT_COVERS_ESTIMATE
 SPLIT_COVERS_HOMOPOLYMER = 0x100  # KMC_HIP_SPLIT_COVERS_HOMOPOLYMER: ask kmc_hip_split_covers before setting the flag (an older library ignores it)
 
 
@@ -99,7 +101,7 @@ SYMBOLS = [
     "kmc_hip_host_register", "kmc_hip_host_unregister", "kmc_hip_host_alloc", "kmc_hip_host_free", "kmc_hip_synchronize",
     "kmc_hip_debug_expand", "kmc_hip_debug_compact", "kmc_hip_debug_split_reads",
     "kmc_hip_split_reads_plan", "kmc_hip_split_reads_emit", "kmc_hip_split_reads_free",
-    "kmc_hip_split_set_map", "kmc_hip_split_part", "kmc_hip_split_covers",
+    "kmc_hip_split_set_map", "kmc_hip_split_part", "kmc_hip_split_covers", "kmc_hip_estimate_open", "kmc_hip_estimate_read", "kmc_hip_estimate_close",
 ]
 
 _LIB = None
@@ -180,6 +182,10 @@ def load():
     L.kmc_hip_debug_split_reads.argtypes = [vp, C.c_int, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint64, u64p]
     if hasattr(L, "kmc_hip_split_covers"):  # added within ABI version 4: a library without it takes file_type 0 and 1 only, and no flags
         L.kmc_hip_split_covers.argtypes = [C.c_uint32]
+    if hasattr(L, "kmc_hip_estimate_open"):  # added within ABI version 4, with KMC_HIP_SPLIT_ESTIMATE
+        L.kmc_hip_estimate_open.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.kmc_hip_estimate_read.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp]
+        L.kmc_hip_estimate_close.argtypes = [vp, C.c_int]
     _LIB = L
     return L
 

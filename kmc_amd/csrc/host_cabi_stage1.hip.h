@@ -347,7 +347,80 @@ int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, 
 	return 0;
 }
 
-int kmc_hip_split_covers(uint32_t what) { return what <= 2 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER ? 1 : 0; }
+int kmc_hip_split_covers(uint32_t what) { return what <= 2 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER || what == KMC_HIP_SPLIT_COVERS_ESTIMATE ? 1 : 0; }
+
+/* ---- histogram estimation while counting (--opt-out-size): the device's share of the reference's CntHashEstimator counters ---- */
+int kmc_hip_estimate_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t s, uint32_t r)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	if (kmer_len < 1 || kmer_len > (uint32_t)S1_MAX_K || s < 1 || s > 16 || r < 8 || r > 27)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_estimate_open: kmer_len 1..256, s 1..16, r 8..27");
+	Dev &d = *ctx->devs[dev];
+	std::lock_guard<std::mutex> lck(d.est_mtx);
+	if (d.d_est) {
+		if (d.est_k == kmer_len && d.est_s == s && d.est_r == r)
+			return 0;
+		return fail(KMC_HIP_EINVAL, "kmc_hip_estimate_open: an estimator with other parameters is open on this device");
+	}
+	const size_t bytes = ((size_t)2 << r) * sizeof(u32);
+	u32 *p = nullptr;
+	HIPCHK(hipMalloc((void **)&p, bytes));
+	hipError_t e = hipMemset(p, 0, bytes);
+	if (e == hipSuccess)
+		e = hipDeviceSynchronize();
+	if (e != hipSuccess) {
+		(void)hipFree(p);
+		return fail_hip("hipMemset(estimator counters)", e);
+	}
+	d.d_est = p;
+	d.est_k = kmer_len, d.est_s = s, d.est_r = r;
+	return 0;
+}
+
+static int estimate_wait_slots(Dev &d) /* what the device's slots have launched adds to the counters */
+{
+	for (auto &sl : d.slot)
+		if (sl.stream)
+			HIPCHK(hipStreamSynchronize(sl.stream));
+	return 0;
+}
+
+int kmc_hip_estimate_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint32_t *dst)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	Dev &d = *ctx->devs[dev];
+	std::lock_guard<std::mutex> lck(d.est_mtx);
+	if (!d.d_est)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_estimate_read: no estimator is open on this device");
+	const uint64_t entries = (uint64_t)2 << d.est_r;
+	if ((count && !dst) || first > entries || count > entries - first)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_estimate_read: [first, first + count) lies outside the 2^(r+1) entries");
+	if (int rc = estimate_wait_slots(d))
+		return rc;
+	if (count)
+		HIPCHK(hipMemcpy(dst, d.d_est + first, (size_t)count * sizeof(u32), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int kmc_hip_estimate_close(kmc_hip_ctx *ctx, int dev)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	Dev &d = *ctx->devs[dev];
+	std::unique_lock<std::mutex> lck(d.est_mtx);
+	/* a split call holds d_est from its check of the flag to its return, without the mutex: the counters outlive every such call */
+	d.est_idle.wait(lck, [&d] { return d.est_users == 0; });
+	if (!d.d_est)
+		return 0;
+	if (int rc = estimate_wait_slots(d))
+		return rc;
+	HIPCHK(hipFree(d.d_est));
+	d.d_est = nullptr;
+	d.est_k = d.est_s = d.est_r = 0;
+	return 0;
+}
 
 int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint8_t *recs,
                        uint64_t recs_capacity, uint64_t *recs_bytes, uint64_t *bin_off, uint64_t *bin_bytes, uint64_t *bin_kmers, uint64_t *bin_superkmers, uint64_t *bin_plus_x,
@@ -360,7 +433,7 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 	if (p->kmer_len < 1 || p->kmer_len > (uint32_t)S1_MAX_K || p->signature_len < 5 || p->signature_len > 11 || p->signature_len > p->kmer_len || p->n_bins < 1 ||
 	    p->n_bins > (uint32_t)S1_MAX_BINS || p->max_x > 3 || p->file_type > 2 || p->part_kind > 1 || (p->max_x && p->kmer_len < 4))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: unsupported parameters");
-	if (p->flags & ~KMC_HIP_SPLIT_HOMOPOLYMER)
+	if (p->flags & ~(KMC_HIP_SPLIT_HOMOPOLYMER | KMC_HIP_SPLIT_ESTIMATE))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: unknown bit in flags");
 	if (p->file_type == 2 && p->part_kind != 0)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: a multi-line FASTA part (file_type 2) is a ReadType::na part: part_kind must be 0");
@@ -371,6 +444,29 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 	Dev &d = *ctx->devs[dev];
 	if (!d.d_sig_map || d.sig_map_entries != (1u << (2 * p->signature_len)) + 1)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: kmc_hip_split_set_map was not called for this signature length");
+	u32 *d_est = nullptr;
+	u32 est_s = 0, est_r = 0;
+	struct EstUser { /* counted from here to the call's return, so that a concurrent kmc_hip_estimate_close cannot free d_est in front of the kernel */
+		Dev *d = nullptr;
+		~EstUser()
+		{
+			if (!d)
+				return;
+			std::lock_guard<std::mutex> lck(d->est_mtx);
+			if (--d->est_users == 0)
+				d->est_idle.notify_all();
+		}
+	} est_user;
+	if (p->flags & KMC_HIP_SPLIT_ESTIMATE) {
+		std::lock_guard<std::mutex> lck(d.est_mtx);
+		if (!d.d_est)
+			return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: KMC_HIP_SPLIT_ESTIMATE without kmc_hip_estimate_open on this device");
+		if (d.est_k != p->kmer_len)
+			return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: KMC_HIP_SPLIT_ESTIMATE: the open estimator has another kmer_len");
+		d_est = d.d_est, est_s = d.est_s, est_r = d.est_r;
+		++d.est_users;
+		est_user.d = &d;
+	}
 	*recs_bytes = 0;
 	Slot &s = d.slot[slot];
 	std::lock_guard<std::mutex> lck(s.mtx);
@@ -421,8 +517,19 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 		*recs_bytes = R.recs_bytes;
 		if (R.recs_bytes > recs_capacity)
 			return fail(KMC_HIP_ECAPACITY, "kmc_hip_split_part: recs_capacity too small, *recs_bytes holds what this part needs");
+		/* nothing below fails because of the part: only now may its k-mers reach the estimator (a call that does not return 0 adds nothing — the
+		 * caller repeats an ECAPACITY call), and in front of the copy down, whose wait is the call's last */
+		if (d_est)
+			s1_estimate_part(be, R.d_raw_codes, R.n_raw, p->kmer_len, est_s, est_r, d_est);
 		if (R.recs_bytes)
 			be.d2h(recs, R.d_recs, R.recs_bytes);
+		else if (d_est) {
+			hipError_t e = hipGetLastError();
+			if (e == hipSuccess)
+				e = hipStreamSynchronize(s.stream);
+			if (e != hipSuccess)
+				return fail_hip("k_s1_nthash_estimate", e);
+		}
 	} catch (const S1BackendFailure &f) {
 		return fail_hip(f.what, f.e);
 	}

@@ -175,6 +175,8 @@ void kmc_hip_destroy(kmc_hip_ctx *ctx)
 			(void)hipFree(d->xchg.p);
 		if (d->d_sig_map)
 			(void)hipFree(d->d_sig_map);
+		if (d->d_est)
+			(void)hipFree(d->d_est);
 		for (auto &a : d->s1_arena)
 			if (a.p)
 				(void)hipFree(a.p);

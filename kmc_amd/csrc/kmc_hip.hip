@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <condition_variable>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -244,6 +245,11 @@ struct Dev {
 	u32 sig_map_entries = 0;
 	std::mutex map_mtx;
 	DBuf s1_arena[N_SLOTS]; /* stage 1: grow-only work area of kmc_hip_split_part, one per stream slot */
+	u32 *d_est = nullptr;   /* stage 1: the two counter arrays of kmc_hip_estimate_open (type 0, then type 1: 2^est_r entries each); nullptr = none open */
+	u32 est_k = 0, est_s = 0, est_r = 0;
+	u32 est_users = 0; /* kmc_hip_split_part calls that took d_est and have not returned: kmc_hip_estimate_close waits for them */
+	std::mutex est_mtx;
+	std::condition_variable est_idle;
 };
 
 u32 counter_bytes(u64 cutoff_max, u64 counter_max) { return kmc_counter_bytes(cutoff_max, counter_max); }

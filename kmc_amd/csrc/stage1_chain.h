@@ -42,6 +42,9 @@ struct S1PartResult {
 	std::vector<u64> bin_off, bin_bytes, bin_sk, bin_kmers, bin_plus_x;
 	u64 n_reads = 0, n_symbols = 0, n_superkmers = 0;
 	u32 device_error = 0;
+	const int8_t *d_raw_codes = nullptr; /* device: the code stream as text -> codes (+ marks) left it, n_raw codes. With -hc the chain cuts another, compacted
+	                                      * stream; this one stays allocated and unchanged: s1_estimate_part hashes it */
+	u64 n_raw = 0;
 };
 enum { S1_CHAIN_OK = 0, S1_CHAIN_UNCOVERED = 1, S1_CHAIN_DEVICE_ERROR = -1, S1_CHAIN_BACKEND_FAILURE = -2 };
 
@@ -137,6 +140,8 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 		} else if (n > stride) /* n_reads of a long-read part: the caller knows whether it took a title off */
 			S1_LAUNCH(B, be, k_s1_mark_raw, dim3(1), dim3(256), d_codes, n, stride, d_has_marks);
 	}
+	R.d_raw_codes = d_codes;
+	R.n_raw = n;
 	/* ---- -hc: the compacted stream (pieces have become sequences of their own: no marks) replaces the code stream for everything below */
 	const u64 *d_cut_marks = d_has_marks;
 	if (P.homopolymer && n) {
@@ -264,6 +269,16 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 	R.d_recs = d_recs;
 	R.recs_bytes = recs_bytes;
 	return S1_CHAIN_OK;
+}
+
+/* Histogram estimation while counting (--opt-out-size): the k-mers of a part's RAW code stream (S1PartResult::d_raw_codes, n_raw) into the two counter arrays
+ * of 2^r entries at d_counters (k_s1_nthash_estimate; s, r: the reference's CntHashEstimator). Not part of s1_split_part: a part whose call fails, or is
+ * repeated with a larger buffer, must add nothing, so the caller launches this once nothing can fail any more, and waits for it with what it waits for last. */
+template <class B> void s1_estimate_part(B &be, const int8_t *d_raw_codes, u64 n, u32 k, u32 s, u32 r, u32 *d_counters)
+{
+	if (n < k)
+		return;
+	S1_LAUNCH(B, be, k_s1_nthash_estimate, dim3((u32)((n + S1_TXT_TILE - 1) / S1_TXT_TILE)), dim3(S1_BLOCK), d_raw_codes, n, k, s, r, s1_nt_seeds(k), d_counters);
 }
 
 #endif

@@ -1026,6 +1026,132 @@ __global__ void __launch_bounds__(S1_BLOCK) k_s1_hc_compact(const int8_t *__rest
 	}
 }
 
+/* ------------------------------------------------------------------------------------------------ histogram estimate while counting (--opt-out-size)
+ * With --opt-out-size the reference hashes every k-mer of every buffer GetSeq returns a second time (CntHashEstimator::Process, called at splitter.cpp:576-577
+ * in front of the homopolymer compression) and counts a sample of the hashes in two arrays of 2^r 32-bit counters; stage 2 picks lut_prefix_len from the
+ * histogram estimated from them (kmc.h:1436-1468), so the database's bytes depend on the counters. Restated as a function of one window of k valid symbols
+ * c_0 .. c_(k-1) (codes 0..3 = A C G T):
+ *     fh = XOR_j rot^(k-1-j)(seed[c_j])      rh = XOR_j rot^j(seed[3 - c_j])      h = min(fh, rh)
+ * where rot turns the low 33 bits and the high 31 bits of a word left by one, each on their own. With pref = h >> (63 - s): pref == 1 adds one to
+ * counters[0][h & (2^r - 1)], (pref >> 1) == 2^(s-1) - 1 adds one to counters[1][same] (both at s = 1 when the two top bits are 0 1); counters wrap at 2^32.
+ * The reference's rolling form is that function and nothing else (an invalid symbol empties its window). The pieces of an over-long line, of a long-read part
+ * and of a multi-line sequence overlap by k - 1 symbols, so every window lies in exactly one return: the estimate is over EVERY window of k valid codes of the
+ * RAW code stream (before k_s1_hc_compact), S1_PIECE_MARK is ignored (a marked code is a valid symbol), separators and N are invalid.
+ *
+ * k_s1_nthash_estimate: one workgroup per tile of S1_TXT_TILE start positions (the tile index is the block index: nothing is carried from tile to tile, a window
+ * depends on k codes), the tile and its k - 1 halo codes in LDS (16 bytes per thread, as the neighbours load). A thread owns a strip of L consecutive start
+ * positions and streams over its L + k - 1 codes as the reference does over a read: the first k - 1 steps fill the window, every later step takes one code in
+ * and one out; an invalid code empties the window, which fills again behind it. A step is 97 instructions in the gfx950 build (scalar ones and the two LDS
+ * byte reads included; the adds of a wave with an accepted lane come on top), with the reference's seeds picked per code from kernel arguments (four tables of four
+ * words: the seeds as they enter fh and rh and as they leave them; two 4-way selects are cheaper than one 16-way select from the reference's out-by-in
+ * table). L = 16 up to k = 64: all 256 threads work, (16 + k - 1) / 16 steps per k-mer = 2.6 at k = 27, about 255 instructions per k-mer. Beyond, L = 64 and
+ * one wave works: fewer, longer strips cost fewer instructions whenever a whole wave is busy (4 x (15 + k) wave-steps per tile with L = 16 against 63 + k
+ * with L = 64), and at k = 255 that is 318 / 64 = 5.0 steps, about 480 instructions per k-mer instead of 1 640. 35 VGPRs, no scratch.
+ * The accepted hashes (2^-s of the k-mers per counter array) of a wave's step are added per distinct index (s1_nt_count): one relaxed agent-scope atomic add
+ * of the number of lanes that hold it; counters: type 0 first, 2^r entries each. */
+struct S1NtSeeds {
+	u64 in_f[4], in_r[4], out_f[4], out_r[4]; /* by code: what an incoming symbol adds to fh, and to rh in front of its turn back; what the outgoing one takes away */
+};
+__host__ __device__ __forceinline__ u64 s1_nt_rot(u64 v)
+{
+	const u64 lo = v & 0x1FFFFFFFFull, hi = v >> 33;
+	return (((lo << 1) | (lo >> 32)) & 0x1FFFFFFFFull) | ((((hi << 1) | (hi >> 30)) & 0x7FFFFFFFull) << 33);
+}
+__host__ __device__ __forceinline__ u64 s1_nt_rot_back(u64 v)
+{
+	const u64 lo = v & 0x1FFFFFFFFull, hi = v >> 33;
+	return ((lo >> 1) | ((lo & 1) << 32)) | (((hi >> 1) | ((hi & 1) << 30)) << 33);
+}
+/* the four base seeds of ntHash (A, C, G, T); everything else is generated from them */
+static inline S1NtSeeds s1_nt_seeds(u32 k)
+{
+	const u64 seed[4] = {0x3c8bfbb395c60474ull, 0x3193c18562a02b4cull, 0x20323ed082572324ull, 0x295549f54be24456ull};
+	S1NtSeeds T;
+	for (u32 c = 0; c < 4; ++c) {
+		u64 turned = seed[c];
+		for (u32 i = 0; i < k; ++i)
+			turned = s1_nt_rot(turned);
+		T.in_f[c] = seed[c];
+		T.out_f[c] = turned;
+		T.in_r[3 - c] = turned;
+		T.out_r[3 - c] = seed[c];
+	}
+	return T;
+}
+__device__ __forceinline__ u64 s1_nt_pick(const u64 (&t)[4], u32 c)
+{
+	const u64 a = c & 1u ? t[1] : t[0], b = c & 1u ? t[3] : t[2];
+	return c & 2u ? b : a;
+}
+
+/* one add per DISTINCT accepted index of the wave, of the number of lanes that hold it: the lanes of a wave walk neighbouring strips, and inside a homopolymer or a
+ * short tandem repeat they all hold the same k-mer. Left to 64 single adds, a k-mer with 2 M copies costs 11.4 ns per copy (measured): ten times the
+ * rest of its part. Called by whole waves only. */
+__device__ __forceinline__ void s1_nt_count(u32 *__restrict__ counters, u32 idx, bool hit)
+{
+	u64 todo = __ballot(hit);
+	while (todo) { /* wave-uniform */
+		const u32 leader = (u32)__ffsll((unsigned long long)todo) - 1u;
+		const u32 at = __shfl(idx, (int)leader);
+		const u64 same = __ballot(hit && idx == at); /* holds the leader's bit: the loop ends */
+		if ((threadIdx.x & 63u) == leader)
+			__hip_atomic_fetch_add(counters + at, (u32)__popcll((unsigned long long)same), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		todo &= ~same;
+	}
+}
+
+__global__ void __launch_bounds__(S1_BLOCK) k_s1_nthash_estimate(const int8_t *__restrict__ codes, u64 n, u32 k, u32 s, u32 r, S1NtSeeds T, u32 *__restrict__ counters)
+{
+	__shared__ __attribute__((aligned(16))) int8_t s_c[S1_TXT_TILE + S1_MAX_K];
+	static_assert(S1_TXT_PER == 16 && S1_MAX_K % 16 == 0, "16-byte loads: the tile by all threads, the halo by the first S1_MAX_K / 16");
+	const u32 tid = threadIdx.x;
+	const u64 tile0 = (u64)blockIdx.x * S1_TXT_TILE;
+#pragma unroll
+	for (u32 part = 0; part < 2; ++part) {
+		if (part && tid >= (u32)S1_MAX_K / 16)
+			break;
+		const u32 off = part * S1_TXT_TILE + tid * 16;
+		const u64 p0 = tile0 + off;
+		uint4 v;
+		if (p0 + 16 <= n)
+			__builtin_memcpy(&v, codes + p0, 16);
+		else {
+			int8_t b[16];
+#pragma unroll
+			for (int j = 0; j < 16; ++j)
+				b[j] = p0 + j < n ? codes[p0 + j] : (int8_t)-1;
+			__builtin_memcpy(&v, b, 16);
+		}
+		__builtin_memcpy(__builtin_assume_aligned(s_c + off, 16), &v, 16);
+	}
+	__syncthreads();
+	const u32 L = k <= 64 ? 16u : 64u;
+	if (tid >= (u32)S1_TXT_TILE / L)
+		return;
+	const u32 q0 = tid * L, q1 = q0 + L + k - 1; /* q1 <= S1_TXT_TILE + S1_MAX_K - 1 */
+	const u32 idx_mask = (1u << r) - 1u, top_shift = 31u - s, ones = (1u << (s - 1)) - 1u;
+	u64 fh = 0, rh = 0;
+	u32 len = 0; /* valid codes in the window, k at most */
+	for (u32 q = q0; q < q1; ++q) {
+		const int8_t cin = s_c[q];
+		const bool ok = cin >= 0, full = len == k;
+		const u32 c = (u32)cin & 3u, o = (u32)s_c[full ? q - k : q] & 3u; /* a full window began at q - k >= q0 */
+		u64 f = s1_nt_rot(fh) ^ s1_nt_pick(T.in_f, c), rv = rh ^ s1_nt_pick(T.in_r, c);
+		if (full) {
+			f ^= s1_nt_pick(T.out_f, o);
+			rv ^= s1_nt_pick(T.out_r, o);
+		}
+		fh = ok ? f : 0ull;
+		rh = ok ? s1_nt_rot_back(rv) : 0ull;
+		len = ok ? (full ? k : len + 1u) : 0u;
+		/* every lane of the wave is here (the strips of a wave are equally long, a wave works whole or not at all) */
+		const u64 h = fh < rh ? fh : rh;
+		const u32 pref = (u32)(h >> 32) >> top_shift, idx = (u32)h & idx_mask;
+		s1_nt_count(counters, idx, len == k && pref == 1u);
+		s1_nt_count(counters + ((size_t)1 << r), idx, len == k && (pref >> 1) == ones);
+	}
+}
+
 /* n_plus_x_recs per bin: how many (k+x)-mer records the reference's stage 2 expands each super-k-mer into (kb_collector.cpp:83-100,
  * kb_collector.h:72-118) — the third sum a CKmerBinCollector keeps, which stage 2 sizes its arrays with. One thread per super-k-mer walks
  * its k-mers comparing the first four symbols of the k-mer with those of its reverse complement. */

@@ -23,6 +23,12 @@ struct SplitApi {
 	                  uint64_t *, uint64_t *, uint64_t *, uint64_t *) = nullptr;
 	const char *(*last_error)(kmc_hip_ctx *) = nullptr;
 	int (*covers)(uint32_t) = nullptr; /* optional: a library without kmc_hip_split_covers takes FASTA and FASTQ only, and no flags */
+	/* optional, added with KMC_HIP_SPLIT_ESTIMATE: a library without them (or whose kmc_hip_split_covers does not know the capability) does not estimate */
+	int (*est_open)(kmc_hip_ctx *, int, uint32_t, uint32_t, uint32_t) = nullptr;
+	int (*est_read)(kmc_hip_ctx *, int, uint64_t, uint64_t, uint32_t *) = nullptr;
+	int (*est_close)(kmc_hip_ctx *, int) = nullptr;
+	std::mutex est_mtx;
+	std::vector<char> est_on; /* per device: an estimator was opened and not drained yet */
 	kmc_hip_ctx *ctx = nullptr;
 	int n_dev = 1, n_slots = 1;
 	std::string err;
@@ -40,11 +46,15 @@ void bind()
 	g_split.split_part = reinterpret_cast<decltype(g_split.split_part)>(dlsym(so, "kmc_hip_split_part"));
 	g_split.last_error = reinterpret_cast<decltype(g_split.last_error)>(dlsym(so, "kmc_hip_last_error"));
 	g_split.covers = reinterpret_cast<decltype(g_split.covers)>(dlsym(so, "kmc_hip_split_covers"));
+	g_split.est_open = reinterpret_cast<decltype(g_split.est_open)>(dlsym(so, "kmc_hip_estimate_open"));
+	g_split.est_read = reinterpret_cast<decltype(g_split.est_read)>(dlsym(so, "kmc_hip_estimate_read"));
+	g_split.est_close = reinterpret_cast<decltype(g_split.est_close)>(dlsym(so, "kmc_hip_estimate_close"));
 	if (!g_split.set_map || !g_split.split_part || !g_split.last_error) {
 		g_split.err = "libkmc_hip.so lacks kmc_hip_split_set_map / kmc_hip_split_part";
 		g_split.ctx = nullptr;
 	}
 	g_split.map_hash.assign((size_t)g_split.n_dev, 0);
+	g_split.est_on.assign((size_t)g_split.n_dev, 0);
 }
 
 struct HipSplitEngine : KmcSplitEngine {
@@ -53,6 +63,7 @@ struct HipSplitEngine : KmcSplitEngine {
 	std::string err;
 	std::vector<uint8_t> recs;
 	std::vector<uint64_t> arrays; /* bin_off | bin_bytes | bin_kmers | bin_superkmers | bin_plus_x */
+	std::vector<uint32_t> drain_buf; /* estimate_drain: one chunk of one device's counters */
 
 	uint64_t map_hash = 0; /* of this run's map: a second KMC run in the same process (library API) with another map must not split with the first one's */
 	HipSplitEngine(const KmcSplitParams &p, int dev, int slot) : P(p), dev(dev), slot(slot)
@@ -68,6 +79,54 @@ struct HipSplitEngine : KmcSplitEngine {
 	bool covers_multiline_fasta() const override { return g_split.ctx && g_split.covers && g_split.covers(2) == 1; }
 	/* a library from before the flag ignores it silently: the query is the only way to know */
 	bool covers_homopolymer_compression() const override { return g_split.ctx && g_split.covers && g_split.covers(KMC_HIP_SPLIT_COVERS_HOMOPOLYMER) == 1; }
+	bool covers_histogram_estimation() const override
+	{
+		return g_split.ctx && g_split.covers && g_split.est_open && g_split.est_read && g_split.est_close && g_split.covers(KMC_HIP_SPLIT_COVERS_ESTIMATE) == 1;
+	}
+	int estimate_open() override
+	{
+		if (!covers_histogram_estimation() || !P.estimate_r) {
+			err = "HIP split engine: no histogram estimation (the library does not cover it, or the engine was made without estimate_s / estimate_r)";
+			return KMC_HIP_EINVAL;
+		}
+		std::lock_guard<std::mutex> lck(g_split.est_mtx);
+		if (int rc = g_split.est_open(g_split.ctx, dev, P.kmer_len, P.estimate_s, P.estimate_r)) { /* a second engine on the device: the same triple, a no-op */
+			err = g_split.last_error(g_split.ctx);
+			return rc;
+		}
+		g_split.est_on[dev] = 1;
+		return 0;
+	}
+	int estimate_drain(uint64_t first, uint64_t count, uint32_t *dst) override
+	{
+		const uint64_t entries = (uint64_t)2 << P.estimate_r;
+		if (!P.estimate_r || !g_split.ctx || count > ((uint64_t)1 << 24) || first > entries || count > entries - first) {
+			err = "HIP split engine: estimate_drain outside the counters, or more than 2^24 entries at once";
+			return KMC_HIP_EINVAL;
+		}
+		std::lock_guard<std::mutex> lck(g_split.est_mtx);
+		drain_buf.resize(count);
+		for (int d = 0; d < g_split.n_dev; ++d) {
+			if (!g_split.est_on[d])
+				continue;
+			if (int rc = g_split.est_read(g_split.ctx, d, first, count, drain_buf.data())) {
+				err = g_split.last_error(g_split.ctx);
+				return rc;
+			}
+			for (uint64_t i = 0; i < count; ++i)
+				dst[i] += drain_buf[i];
+			if (first + count == entries) {
+				g_split.est_on[d] = 0;
+				if (int rc = g_split.est_close(g_split.ctx, d)) {
+					err = g_split.last_error(g_split.ctx);
+					return rc;
+				}
+			}
+		}
+		if (first + count == entries)
+			std::vector<uint32_t>().swap(drain_buf);
+		return 0;
+	}
 	int split_part(const uint8_t *text, uint64_t size, bool long_read, KmcSplitResult &out) override
 	{
 		if (!g_split.ctx) {
@@ -93,7 +152,7 @@ struct HipSplitEngine : KmcSplitEngine {
 		hp.file_type = (uint32_t)P.file_type;
 		hp.line_cap = P.line_cap;
 		hp.part_kind = long_read ? 1u : 0u;
-		hp.flags = P.homopolymer_compressed ? KMC_HIP_SPLIT_HOMOPOLYMER : 0u;
+		hp.flags = (P.homopolymer_compressed ? KMC_HIP_SPLIT_HOMOPOLYMER : 0u) | (P.estimate_r ? KMC_HIP_SPLIT_ESTIMATE : 0u);
 		/* records of real reads take ~0.3 bytes per symbol; text whose k-mers are nearly all their own super-k-mer needs more: second call */
 		if (recs.size() < size + 256ull * (P.n_bins + 1))
 			recs.resize(size + 256ull * (P.n_bins + 1));

@@ -21,7 +21,7 @@
  *
  * FAILS CLOSED (round 5): this worker has no path into the reference's CSplitter. What the engine does not cover stops the run through
  * CCriticalErrorHandler with a message that names it —
- *   per job : input other than FASTA / FASTQ (BAM, KMC; multi-line FASTA unless the engine covers_multiline_fasta()), homopolymer compression (-hc) unless the engine covers_homopolymer_compression(), histogram estimation while counting (--opt-out-size; -e alone runs the reference's estimate-only worker, not this one):
+ *   per job : input other than FASTA / FASTQ (BAM, KMC; multi-line FASTA unless the engine covers_multiline_fasta()), homopolymer compression (-hc) unless the engine covers_homopolymer_compression(), histogram estimation while counting (--opt-out-size) unless the engine covers_histogram_estimation() (-e alone runs the reference's estimate-only worker, not this one):
  *             "use kmc_hip" (the reference's stage 1 + this library's stage 2) is the answer the message gives;
  *   per part: KMC_SPLIT_UNCOVERED — MALFORMED text that CSplitter::GetSeq happens to tolerate (blank lines, a quality string of another length than its
  *             sequence, control characters, a lone '\r').
@@ -29,6 +29,12 @@
  * do the ReadType::na parts of multi-line FASTA (fastq_reader.cpp:399-468, :579-583) with an engine that covers them (file_type 2). With -hc the engine
  * compresses every return of GetSeq on its own, as ProcessReads does (splitter.cpp:575-581); stage 0, the small-k worker and the estimate worker stay the
  * reference's and honour the flag themselves, and n_reads does not depend on it.
+ * With --opt-out-size (ESTIMATE_AND_COUNT_KMERS) the reference's splitter hashes every k-mer a second time into Queues.ntHashEstimator (splitter.cpp:576-577),
+ * an object that exists before the workers are constructed (kmc.h:1277-1293). Here the engine keeps those counters where it splits: every worker opens the
+ * estimator of its engine's device with the object's own s and r, the LAST worker to finish adds the counters of every device into the object's arrays
+ * (in chunks of 64 MB), and kmc.h:1329-1333 then runs the reference's own EstimateHistogram on them — no floating-point line is restated here. s, r and the
+ * counters are private members; they are read through pointers to members obtained by explicit instantiation (access checking does not apply to the
+ * arguments of one): the class, its layout and the reference's sources stay as they are.
  * Only a build with -DKMC_HIP_S1_REFERENCE_FALLBACK (no shipped binary has it; oracle/_ref/kmc_emu_s1_fb is the test build) AND $KMC_HIP_S1_FALLBACK=1
  * in the environment hands such jobs / parts to the reference (CWSplitter_ref / a CSplitter of this thread, our buffers pushed first) and says so on stderr;
  * nothing run that way is covered by this repo's parity claims.
@@ -86,6 +92,35 @@ static inline uint32_t kmc_record_plus_x(const uint8_t *rec, uint32_t kmer_len, 
 	return total + 1 + run / (max_x + 1);
 }
 
+/* pointers to private members of CntHashEstimator, handed out by explicit instantiations (C++14 [temp.explicit]/12); this header is part of ONE translation
+ * unit per binary (-include ahead of kmc_runner.cpp) */
+namespace kmc_hip_est_access {
+template <class Tag> struct Stowed {
+	static typename Tag::type value;
+};
+template <class Tag> typename Tag::type Stowed<Tag>::value;
+template <class Tag, typename Tag::type P> struct Stow {
+	Stow() { Stowed<Tag>::value = P; }
+	static Stow instance;
+};
+template <class Tag, typename Tag::type P> Stow<Tag, P> Stow<Tag, P>::instance;
+struct S {
+	typedef uint32_t CntHashEstimator::*type;
+};
+struct R {
+	typedef uint32_t CntHashEstimator::*type;
+};
+struct Counters {
+	typedef uint32_t *(CntHashEstimator::*type)[2];
+};
+template struct Stow<S, &CntHashEstimator::s>;
+template struct Stow<R, &CntHashEstimator::r>;
+template struct Stow<Counters, &CntHashEstimator::counters>;
+inline uint32_t s_of(CntHashEstimator &e) { return e.*Stowed<S>::value; }
+inline uint32_t r_of(CntHashEstimator &e) { return e.*Stowed<R>::value; }
+inline uint32_t *counters_of(CntHashEstimator &e, int type) { return (e.*Stowed<Counters>::value)[type]; }
+} // namespace kmc_hip_est_access
+
 class CWSplitter {
 	struct BinBuf {
 		uchar *buf = nullptr;
@@ -112,13 +147,13 @@ class CWSplitter {
 	uint64 st_parts = 0, st_long_parts = 0, st_ml_parts = 0, st_uncovered_parts = 0, st_pieces = 0, st_cut_pieces = 0, st_pushes = 0, st_bytes = 0;
 	long long st_engine_ns = 0;
 
-	static const char *uncovered_job(const CKMCParams &P, bool multiline_covered, bool homopolymer_covered)
+	static const char *uncovered_job(const CKMCParams &P, bool multiline_covered, bool homopolymer_covered, bool estimate_covered)
 	{
 		if (P.file_type != InputType::FASTA && P.file_type != InputType::FASTQ && !(P.file_type == InputType::MULTILINE_FASTA && multiline_covered))
 			return "an input format other than FASTA / FASTQ (multi-line FASTA, BAM, KMC)";
 		if (P.homopolymer_compressed && !homopolymer_covered)
 			return "homopolymer compression (-hc)";
-		if (P.estimateHistogramCfg == KMC::EstimateHistogramCfg::ESTIMATE_AND_COUNT_KMERS)
+		if (P.estimateHistogramCfg == KMC::EstimateHistogramCfg::ESTIMATE_AND_COUNT_KMERS && !estimate_covered)
 			return "histogram estimation while counting (--opt-out-size)";
 		return nullptr;
 	}
@@ -195,6 +230,41 @@ class CWSplitter {
 		for (uint32 i = 0; i < (uint32)bins.size(); ++i)
 			push(i);
 	}
+	static bool estimating(CKMCParams &Params, CKMCQueues &Queues)
+	{
+		return Params.estimateHistogramCfg == KMC::EstimateHistogramCfg::ESTIMATE_AND_COUNT_KMERS && Queues.ntHashEstimator;
+	}
+	/* --opt-out-size, by the last worker to finish (every one of the n_splitters workers is constructed and run, kmc.h:1290-1294, :1323-1324): the counters
+	 * of every device, added into the reference's arrays */
+	static std::atomic<int> &finished_workers()
+	{
+		static std::atomic<int> finished{0};
+		return finished;
+	}
+	void drain_estimate()
+	{
+		if (++finished_workers() != (int)params->n_splitters)
+			return;
+		CntHashEstimator &est = *queues->ntHashEstimator;
+		const uint32_t r = kmc_hip_est_access::r_of(est);
+		const uint64_t per_type = (uint64_t)1 << r, chunk = (uint64_t)1 << 24; /* 64 MB of counters at a time */
+		const auto t0 = std::chrono::steady_clock::now();
+		KmcTimeline::mark("splitter: histogram estimate, drain of the device counters starts");
+		for (int type = 0; type < 2; ++type)
+			for (uint64_t at = 0; at < per_type; at += chunk) {
+				const uint64_t cnt = per_type - at < chunk ? per_type - at : chunk;
+				if (int rc = engine->estimate_drain(type * per_type + at, cnt, kmc_hip_est_access::counters_of(est, type) + at)) {
+					std::ostringstream ostr;
+					ostr << "Error: stage-1 split engine failed to hand over the histogram estimate (code " << rc << "): " << engine->last_error();
+					CCriticalErrorHandler::Inst().HandleCriticalError(ostr.str());
+				}
+			}
+		KmcTimeline::mark("splitter: histogram estimate, device counters merged");
+		if (getenv("KMC_HIP_VERBOSE"))
+			fprintf(stderr, "[kmc_hip stage 1] histogram estimate on the device (--opt-out-size): s = %u, r = %u, counters of all devices merged into the reference's "
+			                "estimator in %.3f s\n",
+			        kmc_hip_est_access::s_of(est), r, std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count() * 1e-9);
+	}
 	static KmcSplitEngine *make_engine(CKMCParams &Params, CKMCQueues &Queues)
 	{
 		KmcSplitParams sp;
@@ -207,6 +277,10 @@ class CWSplitter {
 		sp.line_cap = (uint64_t)Params.mem_part_pmm_reads;
 		sp.sig_to_bin = Queues.s_mapper->GetMap();
 		sp.homopolymer_compressed = Params.homopolymer_compressed ? 1 : 0;
+		if (estimating(Params, Queues)) {
+			sp.estimate_s = kmc_hip_est_access::s_of(*Queues.ntHashEstimator);
+			sp.estimate_r = kmc_hip_est_access::r_of(*Queues.ntHashEstimator);
+		}
 		static std::atomic<int> next_idx{0};
 		return kmc_make_split_engine(sp, next_idx++ % (int)Params.n_splitters, (int)Params.n_splitters);
 	}
@@ -225,9 +299,10 @@ public:
 		max_x = Params.max_x;
 		both_strands = Params.both_strands;
 		buffer_size = Params.bin_part_size;
-		if (Params.file_type == InputType::MULTILINE_FASTA || Params.homopolymer_compressed)
-			engine.reset(make_engine(Params, Queues)); /* whether the format / the compression is covered is the engine's answer */
-		if (const char *what = uncovered_job(Params, engine && engine->covers_multiline_fasta(), engine && engine->covers_homopolymer_compression())) {
+		if (Params.file_type == InputType::MULTILINE_FASTA || Params.homopolymer_compressed || estimating(Params, Queues))
+			engine.reset(make_engine(Params, Queues)); /* whether the format / the compression / the estimate is covered is the engine's answer */
+		if (const char *what = uncovered_job(Params, engine && engine->covers_multiline_fasta(), engine && engine->covers_homopolymer_compression(),
+		                                     engine && engine->covers_histogram_estimation())) {
 #ifdef KMC_HIP_S1_REFERENCE_FALLBACK
 			const char *fb = getenv("KMC_HIP_S1_FALLBACK");
 			if (fb && fb[0] == '1') {
@@ -254,6 +329,15 @@ public:
 			engine.reset(make_engine(Params, Queues));
 		if (!engine)
 			CCriticalErrorHandler::Inst().HandleCriticalError("Error: no stage-1 split engine available");
+		/* every worker of a run is constructed before the readers start (kmc.h:1290-1316), so before any worker can find the part queue completed and finish:
+		 * counting from zero here serves a second run in the same process (library API), also behind a run whose workers left through the error handler */
+		finished_workers() = 0;
+		if (estimating(Params, Queues))
+			if (int rc = engine->estimate_open()) {
+				std::ostringstream ostr;
+				ostr << "Error: stage-1 split engine could not open the histogram estimator (code " << rc << "): " << engine->last_error();
+				CCriticalErrorHandler::Inst().HandleCriticalError(ostr.str());
+			}
 	}
 
 	void operator()()
@@ -314,6 +398,8 @@ public:
 		}
 		push_all();
 		bpq->mark_completed();
+		if (estimating(*params, *queues))
+			drain_estimate();
 		engine.reset();
 		KmcTimeline::mark_first_last(nullptr, "splitter: last worker done");
 		if (getenv("KMC_HIP_VERBOSE"))

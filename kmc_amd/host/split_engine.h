@@ -25,6 +25,8 @@ struct KmcSplitParams {
 	const int32_t *sig_to_bin; /* CSignatureMapper's map, 4^signature_len + 1 entries (s_mapper.h:232) */
 	int homopolymer_compressed = 0; /* -hc: every return of GetSeq is compressed on its own (splitter.cpp:424-435, :575-581); only for an engine that
 	                                 * covers_homopolymer_compression() */
+	uint32_t estimate_s = 0, estimate_r = 0; /* --opt-out-size: s and r of the reference's CntHashEstimator (k is kmer_len); both 0 = off. Only for an engine
+	                                          * that covers_histogram_estimation(): every part's k-mers then go to the estimator of estimate_open() */
 };
 
 /* valid until the next split_part() on the same engine */
@@ -49,6 +51,15 @@ struct KmcSplitEngine {
 	virtual bool covers_multiline_fasta() const { return false; }
 	/* -hc (KmcSplitParams::homopolymer_compressed), with every file type and with long-read parts */
 	virtual bool covers_homopolymer_compression() const { return false; }
+	/* histogram estimation while counting (--opt-out-size; KmcSplitParams::estimate_s / _r): the engine keeps the two counter arrays of CntHashEstimator
+	 * (ntHashWrapper.h: 2 x 2^r 32-bit counters, type 0 first) wherever its parts are split, and adds every part's k-mers to them.
+	 * estimate_open : makes the (zeroed) counters of this engine's device; once per engine, in front of its first part. 0 or an error code.
+	 * estimate_drain: when every engine of the run has split its last part: ADDS entries [first, first + count) of the counters of every device an
+	 *                 estimator was opened on to dst[0 .. count) (wrapping at 2^32), count <= 2^24 (64 MB); the call that takes the last entry also closes
+	 *                 the estimators. 0 or an error code. */
+	virtual bool covers_histogram_estimation() const { return false; }
+	virtual int estimate_open() { return -1; }
+	virtual int estimate_drain(uint64_t /*first*/, uint64_t /*count*/, uint32_t * /*dst*/) { return -1; }
 };
 
 /* Provided by exactly one engine implementation linked into the binary. */
