@@ -316,6 +316,14 @@ void kmc_hip_split_reads_free(kmc_hip_ctx *ctx, kmc_hip_s1_plan *plan);
  * file_type 2 = a multi-line FASTA part as CFastqReader::GetPartFromMultilneFasta cuts it (ReadType::na, fastq_reader.cpp:399-468: a title keeps its
  * run of end-of-line bytes, the sequence text has none, a part may start inside a sequence); it is split as CSplitter::GetSeq's MULTILINE_FASTA branch
  * does (splitter.cpp:304-323), *n_reads = titles in the part, and part_kind must be 0.
+ * file_type 4 = a part of BAM alignment records as the reference's BAM readers hand them out (ReadType::na, fastq_reader.cpp:191-362: BGZF inflated and the
+ * file header taken off on the host; whole records, the first one at byte 0), smaller than 2 GiB, part_kind 0. It is split as CSplitter::GetSeq's BAM branch
+ * does (splitter.cpp:326-419): records with flag 0x100 or 0x800 are skipped, every other record is one read (*n_reads; one without bases too), its 4-bit
+ * bases decoded (A C G T, all else invalid) and, with both_strands 0 and flag 0x10, reversed and complemented. KMC_HIP_UNCOVERED: the records do not end
+ * exactly at the part's end, a block_size below what its header, name, cigar, bases and qualities take (a negative one included), a negative l_seq, a header
+ * that runs past the part, or an included record of line_cap bases or more (the reference writes those past its buffer). Works with every flag. The value is 4,
+ * not 3: callers of libraries from before BAM use 3 as the file type that is KMC_HIP_EINVAL and that kmc_hip_split_covers answers 0 for, and it stays so (as
+ * 0x101 does among the capabilities).
  * Returns 0, a negative KMC_HIP_E* code, or KMC_HIP_UNCOVERED: the text is MALFORMED in a way CSplitter::GetSeq tolerates and the kernels do not
  * reproduce (blank lines, quality of another length than its sequence, a lone '\r', control characters; multi-line FASTA: a part that ends inside a
  * title line) — nothing was produced; the stage-1 worker
@@ -325,7 +333,7 @@ void kmc_hip_split_reads_free(kmc_hip_ctx *ctx, kmc_hip_s1_plan *plan);
 typedef struct kmc_hip_split_params {
 	uint32_t kmer_len, signature_len, n_bins, max_x; /* max_x: CKMCParams::max_x (0..3) */
 	uint32_t both_strands;
-	uint32_t file_type;                              /* 0 = FASTA (one line per sequence), 1 = FASTQ, 2 = multi-line FASTA (-fm) */
+	uint32_t file_type;                              /* 0 = FASTA (one line per sequence), 1 = FASTQ, 2 = multi-line FASTA (-fm), 4 = BAM records (-fbam); 3 stays unknown */
 	uint64_t line_cap;                               /* CKMCParams::mem_part_pmm_reads */
 	uint32_t part_kind;                              /* 0 = whole records (ReadType::normal_read), 1 = ReadType::long_read */
 	uint32_t flags;                                  /* KMC_HIP_SPLIT_*; any other bit is KMC_HIP_EINVAL. (Named `reserved`, to be 0, before the first flag.) */

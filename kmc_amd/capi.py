@@ -77,6 +77,7 @@ class SplitParams(C.Structure):
                 ("file_type", C.c_uint32), ("line_cap", C.c_uint64), ("part_kind", C.c_uint32), ("flags", C.c_uint32)]
 
 
+SPLIT_FILE_BAM = 4  # kmc_hip_split_params.file_type: a part of BAM alignment records (-fbam); ask kmc_hip_split_covers(4) first (3 stays an unknown file type)
 SPLIT_HOMOPOLYMER = 1  # KMC_HIP_SPLIT_HOMOPOLYMER: flags bit 0, -hc
 SPLIT_ESTIMATE = 4  # KMC_HIP_SPLIT_ESTIMATE: flags bit 2, --opt-out-size (the part's k-mers go to the estimator of kmc_hip_estimate_open)
 SPLIT_COVERS_ESTIMATE = 0x102  # KMC_HIP_SPLIT_COVERS_ESTIMATE

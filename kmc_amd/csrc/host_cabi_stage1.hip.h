@@ -347,7 +347,7 @@ int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, 
 	return 0;
 }
 
-int kmc_hip_split_covers(uint32_t what) { return what <= 2 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER || what == KMC_HIP_SPLIT_COVERS_ESTIMATE ? 1 : 0; }
+int kmc_hip_split_covers(uint32_t what) { return what <= 2 || what == 4 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER || what == KMC_HIP_SPLIT_COVERS_ESTIMATE ? 1 : 0; }
 
 /* ---- histogram estimation while counting (--opt-out-size): the device's share of the reference's CntHashEstimator counters ---- */
 int kmc_hip_estimate_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t s, uint32_t r)
@@ -431,12 +431,16 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 	if (!p || (size && !text) || !recs || !recs_bytes || !bin_off || !bin_bytes || !bin_kmers || !bin_superkmers || !bin_plus_x || !n_reads || slot < 0 || slot >= N_SLOTS)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: bad argument");
 	if (p->kmer_len < 1 || p->kmer_len > (uint32_t)S1_MAX_K || p->signature_len < 5 || p->signature_len > 11 || p->signature_len > p->kmer_len || p->n_bins < 1 ||
-	    p->n_bins > (uint32_t)S1_MAX_BINS || p->max_x > 3 || p->file_type > 2 || p->part_kind > 1 || (p->max_x && p->kmer_len < 4))
+	    p->n_bins > (uint32_t)S1_MAX_BINS || p->max_x > 3 || p->file_type > 4 || p->file_type == 3 || p->part_kind > 1 || (p->max_x && p->kmer_len < 4))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: unsupported parameters");
 	if (p->flags & ~(KMC_HIP_SPLIT_HOMOPOLYMER | KMC_HIP_SPLIT_ESTIMATE))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: unknown bit in flags");
 	if (p->file_type == 2 && p->part_kind != 0)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: a multi-line FASTA part (file_type 2) is a ReadType::na part: part_kind must be 0");
+	if (p->file_type == 4 && p->part_kind != 0)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: a part of BAM records (file_type 4) is a ReadType::na part: part_kind must be 0");
+	if (p->file_type == 4 && size >= S1_BAM_MAX_PART)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: a part of BAM records (file_type 4) must be smaller than 2 GiB");
 	/* a configuration limit, not a property of the text: the pieces of an over-long line are cut at workgroup windows (stage1_chain.h) */
 	if (p->line_cap < (uint64_t)p->kmer_len + S1_WG_TILE + 2)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: line_cap (mem_part_pmm_reads) is too small for the device splitter: it needs kmer_len + " + std::to_string(S1_WG_TILE + 2) +
@@ -474,7 +478,9 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 	 * (2 B per symbol at the first guess) + records (~0.3 B per symbol) + per-bin arrays; -hc: the compacted code stream (1 B per symbol + k per piece
 	 * start, which are more than 4096 symbols apart: under 2 B per byte of text with its look-back words) */
 	const bool hc = (p->flags & KMC_HIP_SPLIT_HOMOPOLYMER) != 0;
-	if (int rc = ensure(d.s1_arena[slot], (size_t)size * ((p->file_type == 2 ? 10 : 8) + (hc ? 2 : 0)) + ((size_t)32 << 20)))
+	/* BAM records: two bases per byte, so codes, super-k-mers and records double; + 4 B per 36 B of text for the record offsets */
+	const size_t per_byte = p->file_type == 4 ? 14 + (hc ? 4 : 0) : (p->file_type == 2 ? 10 : 8) + (hc ? 2 : 0);
+	if (int rc = ensure(d.s1_arena[slot], (size_t)size * per_byte + ((size_t)32 << 20)))
 		return rc;
 	S1HipBackend be;
 	be.stream = s.stream;
@@ -488,6 +494,7 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 	sp.both_strands = p->both_strands ? 1u : 0u;
 	sp.lines_per_record = p->file_type == 1 ? 4u : 2u;
 	sp.multiline_fasta = p->file_type == 2;
+	sp.bam = p->file_type == 4;
 	sp.homopolymer = hc;
 	sp.line_cap = p->line_cap;
 	sp.d_sig_to_bin = d.d_sig_map;

@@ -33,7 +33,9 @@ struct S1PartParams {
 	bool sorted_emit = false;                                 /* records through a sort by bin (k_s1_emit_sorted) instead of k_s1_emit: bins in read order */
 	bool multiline_fasta = false;                             /* a multi-line FASTA part (ReadType::na, GetSeq splitter.cpp:304-323): k_s1_ml_text_to_codes;
 	                                                           * lines_per_record is not used */
-	bool homopolymer = false;                                 /* -hc: every return of GetSeq — a line, or one PIECE of an over-long line / a long-read part — is
+	bool bam = false;                                         /* a part of BAM alignment records (ReadType::na, GetSeq splitter.cpp:326-419): k_s1_bam_chain + k_s1_bam_decode;
+	                                                           * lines_per_record is not used, no piece marks are made */
+	bool homopolymer = false;                               /* -hc: every return of GetSeq — a line, or one PIECE of an over-long line / a long-read part — is
 	                                                           * homopolymer-compressed on its own (splitter.cpp:424-435, :575-581): k_s1_hc_compact in front of the cut */
 };
 struct S1PartResult {
@@ -87,7 +89,41 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 	u64 n;
 	int8_t *d_codes;
 	u32 err;
-	if (P.multiline_fasta) {
+	if (P.bam) {
+		/* ---- BAM records -> codes: the record starts (one chain from offset 0 to the part's end), then the bases. No piece marks: a record of line_cap bases
+		 * or more is not taken */
+		if (size >= S1_BAM_MAX_PART)
+			return S1_CHAIN_UNCOVERED; /* record offsets are 32-bit words; kmc_hip_split_part refuses such a call by name */
+		const u32 tiles = (u32)((size + S1_BAM_TILE - 1) / S1_BAM_TILE);
+		const u64 rec_cap = size / S1_BAM_MIN_HOP + 1, out_cap = 2 * size + 16;
+		u32 *d_rec = (u32 *)be.alloc_uninit(rec_cap * 4);
+		u64 *d_bstat = (u64 *)be.alloc((size_t)tiles * 8);
+		d_codes = (int8_t *)be.alloc_uninit(out_cap + 16);
+		S1_LAUNCH(B, be, k_s1_bam_chain, dim3(tiles), dim3(S1_BLOCK), d_text, size, d_bstat, d_ticket, d_rec, rec_cap, d_small, d_err);
+		if (!be.d2h(small, d_small, sizeof small))
+			return S1_CHAIN_BACKEND_FAILURE;
+		err = (u32)(small[3] >> 32);
+		const u64 n_rec = small[0];
+		if (!err && n_rec) {
+			const u32 dt = (u32)((n_rec + S1_BLOCK - 1) / S1_BLOCK);
+			u64 *d_dstat = (u64 *)be.alloc((size_t)dt * 8);
+			be.zero(d_ticket, 4);
+			S1_LAUNCH(B, be, k_s1_bam_decode, dim3(dt), dim3(S1_BLOCK), d_text, size, (const u32 *)d_rec, n_rec, P.both_strands, P.line_cap, d_dstat, d_ticket, d_codes, out_cap,
+			          d_small, d_err);
+			if (!be.d2h(small, d_small, sizeof small))
+				return S1_CHAIN_BACKEND_FAILURE;
+			err = (u32)(small[3] >> 32);
+		}
+		if (err & (S1_TEXT_BAD | KERR_CAPACITY))
+			return S1_CHAIN_UNCOVERED;
+		if (err) {
+			R.device_error = err;
+			return S1_CHAIN_DEVICE_ERROR;
+		}
+		n = n_rec ? small[1] : 0;
+		R.n_symbols = n;
+		R.n_reads = n_rec ? small[0] : 0;
+	} else if (P.multiline_fasta) {
 		/* ---- text -> codes, multi-line FASTA: per-sequence arrays sized by titles (two bytes each at least), not by lines */
 		const u64 seq_cap = size / 2 + 2;
 		const u32 tiles = (u32)((size + S1_TXT_TILE - 1) / S1_TXT_TILE);

@@ -1026,6 +1026,336 @@ __global__ void __launch_bounds__(S1_BLOCK) k_s1_hc_compact(const int8_t *__rest
 	}
 }
 
+/* ------------------------------------------------------------------------------------------------ BAM records (-fbam)
+ * The reference's BAM readers inflate BGZF on the host, take the file header off and hand the splitter parts that hold whole alignment records only
+ * (fastq_reader.cpp:191-362, ReadType::na). CSplitter::GetSeq's BAM branch (splitter.cpp:326-419) walks them: a record is
+ *     block_size:i32 | refID pos | bin_mq_nl:u32 | flag_nc:u32 | l_seq:i32 | next_refID next_pos tlen | name | cigar | (l_seq + 1) / 2 nibble bytes | qualities | tags
+ * and the next one starts 4 + block_size bytes on. l_read_name is the low byte of bin_mq_nl, n_cigar_op the low half of flag_nc, the flags its high half. A
+ * record with flag 0x100 or 0x800 is skipped (not counted); any other is one read, its bases decoded from "=ACMGRSVTWYHKDBN" (A C G T -> 0..3, all else
+ * invalid), first base in the high nibble; without both_strands a record with flag 0x10 is written back to front and complemented.
+ * The reference writes a record's bases into a buffer of line_cap symbols without a bound, so an included record with l_seq >= line_cap has no result to
+ * reproduce: S1_TEXT_BAD, as is a chain that does not end exactly at the part's end, a block_size below 32 + name + cigar + bases + qualities (a negative one
+ * included), a negative l_seq and a header that runs past the part. Every byte read is inside [0, n); no piece marks are made.
+ *
+ * k_s1_bam_chain finds the record starts. The chain has no entry points but offset 0, and one lane hopping through global memory costs about a microsecond per
+ * record (see k_parse_packs in kernels.hip.h). Ticketed tiles of S1_BAM_TILE bytes: a tile first resolves in LDS, for EVERY byte offset o of the tile taken
+ * as a record start, where the chain from o leaves the tile and after how many records — one 64-bit entry per offset (low half: offset relative to the tile,
+ * S1_BAM_BAD when the chain meets a block_size below 32 or runs past the part; high half: hops), by pointer doubling: a hop is 36 bytes at least, so the
+ * S1_BAM_TILE / 36 hops a tile can hold are done in S1_BAM_ROUNDS rounds, fewer when no chain is left inside (real records are hundreds of bytes). Only then
+ * does it wait for the tile in front, which hands over the true entry offset and the number of records before it in ONE relaxed agent-scope 64-bit word that
+ * is flag, count and offset at once (nothing else is communicated, so nothing needs ordering); one LDS read later the tile publishes its own word. A record
+ * longer than a tile passes through the tiles it covers (entry at or past their end: they publish what they received). Off that critical path one lane then
+ * walks the true chain through the tile's bytes in LDS and writes the record offsets, in order, to rec_off (u32: the chain refuses parts of 2 GiB and more).
+ * A tile that finds its entry bad raises S1_TEXT_BAD and publishes n, so that no later tile waits or walks. totals[0] = records. status: one zeroed u64 per tile. */
+constexpr int S1_BAM_PER = 32, S1_BAM_TILE = S1_BLOCK * S1_BAM_PER;
+constexpr u32 S1_BAM_MIN_HOP = 36; /* the block_size word + the 32 fixed bytes behind it */
+constexpr int S1_BAM_ROUNDS = 8;
+static_assert((1 << S1_BAM_ROUNDS) >= S1_BAM_TILE / (int)S1_BAM_MIN_HOP + 1, "pointer doubling covers the longest chain inside a tile");
+constexpr u32 S1_BAM_BAD = 0xFFFFFFFFu;
+constexpr u64 S1_BAM_MAX_PART = 1ull << 31;
+constexpr u64 S1_BAM_ST_FLAG = 1ull << 63, S1_BAM_ST_OFF_MASK = (1ull << 36) - 1; /* [63] published | [62:36] records before | [35:0] entry offset in the part */
+
+/* the little-endian 32-bit word at byte `at` of an LDS array that is readable up to the aligned word behind it */
+__device__ __forceinline__ u32 s1_bam_lds_word(const uint8_t *s, u32 at)
+{
+	const u32 *w = reinterpret_cast<const u32 *>(s);
+	const u64 both = ((u64)w[(at >> 2) + 1] << 32) | w[at >> 2];
+	return (u32)(both >> (8u * (at & 3u)));
+}
+/* where the record at offset o of the tile ends, relative to the tile; S1_BAM_BAD if it cannot be one */
+__device__ __forceinline__ u32 s1_bam_hop(const uint8_t *s_b, u32 o, u64 tile0, u64 n)
+{
+	if (tile0 + o + 4 > n)
+		return S1_BAM_BAD;
+	const int bs = (int)s1_bam_lds_word(s_b, o);
+	if (bs < 32 || tile0 + o + 4 + (u64)bs > n)
+		return S1_BAM_BAD;
+	return o + 4u + (u32)bs;
+}
+
+__global__ void __launch_bounds__(S1_BLOCK) k_s1_bam_chain(const uint8_t *__restrict__ text, u64 n, u64 *status, u32 *ticket_ctr, u32 *__restrict__ rec_off, u64 rec_cap,
+                                                            u64 *totals, u32 *err)
+{
+	__shared__ __attribute__((aligned(16))) uint8_t s_b[S1_BAM_TILE + 16]; /* the tile and the bytes a block_size word at its end reaches into */
+	__shared__ u64 s_j[S1_BAM_TILE];
+	__shared__ u32 s_ticket, s_moved[2];
+	__shared__ u64 s_entry, s_first;
+	const u32 tid = threadIdx.x;
+	if (tid == 0) {
+		s_ticket = atomicAdd(ticket_ctr, 1u);
+		s_moved[0] = s_moved[1] = 0;
+	}
+	__syncthreads();
+	const u32 tile = s_ticket;
+	const u32 num_tiles = (u32)((n + S1_BAM_TILE - 1) / S1_BAM_TILE);
+	if (tile >= num_tiles)
+		return;
+	const u64 tile0 = (u64)tile * S1_BAM_TILE;
+	const u32 tlen = n - tile0 < (u64)S1_BAM_TILE ? (u32)(n - tile0) : (u32)S1_BAM_TILE;
+	static_assert(S1_BAM_PER % 16 == 0, "16-byte loads");
+#pragma unroll
+	for (u32 i = 0; i < (u32)S1_BAM_PER / 16 + 1; ++i) {
+		const u32 off = (i * S1_BLOCK + tid) * 16;
+		if (off >= (u32)S1_BAM_TILE + 16)
+			break;
+		const u64 p = tile0 + off;
+		uint4 v;
+		if (p + 16 <= n)
+			__builtin_memcpy(&v, text + p, 16);
+		else {
+			uint8_t b[16];
+#pragma unroll
+			for (int j = 0; j < 16; ++j)
+				b[j] = p + j < n ? text[p + j] : (uint8_t)0;
+			__builtin_memcpy(&v, b, 16);
+		}
+		__builtin_memcpy(__builtin_assume_aligned(s_b + off, 16), &v, 16);
+	}
+	__syncthreads();
+	/* one hop from every offset (thread t takes offsets t, t + 256, ...: neighbouring lanes, neighbouring LDS words) */
+#pragma unroll 4
+	for (u32 j = 0; j < (u32)S1_BAM_PER; ++j) {
+		const u32 o = j * S1_BLOCK + tid;
+		s_j[o] = (1ull << 32) | (o < tlen ? s1_bam_hop(s_b, o, tile0, n) : S1_BAM_BAD);
+	}
+	__syncthreads();
+	for (u32 r = 0; r < (u32)S1_BAM_ROUNDS; ++r) {
+		u64 v[S1_BAM_PER];
+		bool moved = false;
+#pragma unroll
+		for (u32 j = 0; j < (u32)S1_BAM_PER; ++j) {
+			u64 a = s_j[j * S1_BLOCK + tid];
+			if ((u32)a < tlen) { /* still inside: take the hops of where it stands */
+				const u64 b = s_j[(u32)a];
+				a = (((a >> 32) + (b >> 32)) << 32) | (u32)b;
+				moved = true;
+			}
+			v[j] = a;
+		}
+		if (moved)
+			s_moved[r & 1] = 1;
+		__syncthreads();
+#pragma unroll
+		for (u32 j = 0; j < (u32)S1_BAM_PER; ++j)
+			s_j[j * S1_BLOCK + tid] = v[j];
+		if (tid == 0)
+			s_moved[(r + 1) & 1] = 0;
+		__syncthreads();
+		if (!s_moved[r & 1])
+			break;
+	}
+	/* ---- the entry from the tile in front, this tile's word */
+	if (tid == 0) {
+		u64 entry = 0, before = 0;
+		if (tile) {
+			LbWatch watch;
+			u64 v;
+			while (!((v = ld_agent(&status[tile - 1])) & S1_BAM_ST_FLAG)) {
+				if (lb_blocked(watch, err)) {
+					lb_gave_up(watch, err, KERR_WATCHDOG | KERR_AT_STAGE1, 0u, tile, (long long)tile - 1, num_tiles);
+					v = n; /* nothing to walk, here and behind */
+					break;
+				}
+				__builtin_amdgcn_s_sleep(1);
+			}
+			entry = v & S1_BAM_ST_OFF_MASK;
+			before = (v & ~S1_BAM_ST_FLAG) >> 36;
+		}
+		u64 exit_at = entry, here = 0;
+		bool bad = false;
+		if (entry < tile0 + tlen) { /* tile0 <= entry: it is where a chain left the tiles in front */
+			const u64 a = s_j[(u32)(entry - tile0)];
+			if ((u32)a == S1_BAM_BAD || (u32)a < tlen)
+				bad = true;
+			else {
+				exit_at = tile0 + (u32)a;
+				here = a >> 32;
+			}
+		}
+		if (tile == num_tiles - 1 && exit_at != n)
+			bad = true; /* the chain ends exactly at the end of the part (an entry beyond it arrives here too) */
+		if (bad) {
+			atomicOr(err, S1_TEXT_BAD);
+			exit_at = n;
+			here = 0;
+		}
+		st_agent(&status[tile], S1_BAM_ST_FLAG | ((before + here) << 36) | exit_at);
+		if (tile == num_tiles - 1)
+			totals[0] = before + here;
+		s_entry = bad ? n : entry;
+		s_first = before;
+	}
+	__syncthreads();
+	/* ---- the true starts of this tile, in order */
+	if (tid == 0) {
+		u64 idx = s_first;
+		for (u64 q = s_entry; q < tile0 + tlen && idx < rec_cap; ++idx) {
+			const u32 to = s1_bam_hop(s_b, (u32)(q - tile0), tile0, n);
+			if (to == S1_BAM_BAD)
+				break; /* reported above */
+			rec_off[idx] = (u32)q;
+			q = tile0 + to;
+		}
+	}
+}
+
+/* k_s1_bam_decode: the records at rec_off[0 .. n_rec) -> the code stream of the kernels above: for every included record with bases ONE negative separator
+ * and its l_seq codes (k_s1_ml_text_to_codes's convention for a title: the separator stands in front of its sequence); an included record without bases is
+ * counted and writes nothing. Ticketed tiles of S1_BLOCK records: a thread checks one record's header (the rules in the comment above), one block sum + one
+ * decoupled look-back over (codes | included records << 34) give the tile's place in the stream, then the tile's bases are decoded by all threads in units of
+ * 16 codes = one ALIGNED 16-byte store: a unit finds its record by bisection over the tile's unit counts in LDS, loads the 8 or 9 nibble bytes under it at once
+ * and turns them in registers (back to front and complemented for a reversed record). Units at the ends of a record store bytes.
+ * totals[0] = reads, totals[1] = codes; out_cap bounds the stores (2 n + 16 always suffices: a record's 36 bytes pay for its separator). status: one zeroed
+ * u64 per tile. */
+constexpr u64 S1_BAM_CNT_SHIFT = 34, S1_BAM_LEN_MASK = (1ull << S1_BAM_CNT_SHIFT) - 1;
+
+__device__ __forceinline__ u32 s1_bam_u32(const uint8_t *p)
+{
+	u32 v;
+	__builtin_memcpy(&v, p, 4);
+	return v;
+}
+
+__global__ void __launch_bounds__(S1_BLOCK) k_s1_bam_decode(const uint8_t *__restrict__ text, u64 n, const u32 *__restrict__ rec_off, u64 n_rec, u32 both_strands, u64 line_cap,
+                                                             u64 *status, u32 *ticket_ctr, int8_t *__restrict__ codes, u64 out_cap, u64 *totals, u32 *err)
+{
+	__shared__ u64 s_tmp64[S1_BLOCK / 64 + 1];
+	__shared__ u32 s_tmp[S1_BLOCK / 64 + 1];
+	__shared__ u64 s_carry;
+	__shared__ u32 s_ticket;
+	__shared__ u32 s_src[S1_BLOCK], s_len[S1_BLOCK], s_unit0[S1_BLOCK + 1]; /* first nibble byte | l_seq, bit 31: reversed | units before the record */
+	__shared__ u64 s_at[S1_BLOCK];                                            /* the record's first code in the stream */
+	const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	if (tid == 0)
+		s_ticket = atomicAdd(ticket_ctr, 1u);
+	__syncthreads();
+	const u32 tile = s_ticket;
+	const u32 num_tiles = (u32)((n_rec + S1_BLOCK - 1) / S1_BLOCK);
+	if (tile >= num_tiles)
+		return;
+	const u64 r = (u64)tile * S1_BLOCK + tid;
+	u32 l_seq = 0, src = 0, rev = 0, included = 0;
+	if (r < n_rec) {
+		const u64 off = rec_off[r];
+		bool bad = off + S1_BAM_MIN_HOP > n; /* the header runs past the part */
+		if (!bad) {
+			const int bs = (int)s1_bam_u32(text + off), ls = (int)s1_bam_u32(text + off + 20);
+			const u32 bin_mq_nl = s1_bam_u32(text + off + 12), flag_nc = s1_bam_u32(text + off + 16);
+			const u32 l_name = bin_mq_nl & 255u, n_cigar = flag_nc & 0xFFFFu, flags = flag_nc >> 16;
+			bad = bs < 32 || ls < 0;
+			if (!bad) {
+				const u64 front = 32ull + l_name + 4ull * n_cigar, need = front + ((u64)ls + 1) / 2 + (u64)ls;
+				bad = (u64)bs < need || off + 4 + (u64)bs > n;
+				if (!bad && !(flags & 0x900u)) { /* neither secondary nor supplementary */
+					if ((u64)ls >= line_cap)
+						bad = true; /* the reference's buffer holds line_cap symbols */
+					else {
+						included = 1;
+						l_seq = (u32)ls;
+						src = (u32)(off + 4 + front);
+						rev = !both_strands && (flags & 0x10u) ? 1u : 0u;
+					}
+				}
+			}
+		}
+		if (bad) {
+			atomicOr(err, S1_TEXT_BAD);
+			included = l_seq = 0;
+		}
+	}
+	const u64 mine = (l_seq ? (u64)l_seq + 1 : 0ull) | ((u64)included << S1_BAM_CNT_SHIFT);
+	u64 tile_sum;
+	const u64 before = block_excl_sum<S1_BLOCK / 64, u64>(mine, s_tmp64, tile_sum);
+	if (wave == 0) {
+		const u64 excl = lookback64(status, tile, tile_sum, lane, err, KERR_WATCHDOG | KERR_AT_STAGE1);
+		if (lane == 0) {
+			s_carry = excl;
+			if (tile == num_tiles - 1) {
+				totals[0] = (excl + tile_sum) >> S1_BAM_CNT_SHIFT;
+				totals[1] = (excl + tile_sum) & S1_BAM_LEN_MASK;
+			}
+		}
+	}
+	__syncthreads();
+	const u64 tile_at = s_carry & S1_BAM_LEN_MASK;
+	if (tile_at + (tile_sum & S1_BAM_LEN_MASK) > out_cap) { /* tile-uniform; cannot happen with the chain's sizing */
+		if (tid == 0)
+			atomicOr(err, KERR_CAPACITY);
+		return;
+	}
+	const u64 at = tile_at + (before & S1_BAM_LEN_MASK) + 1; /* behind the separator */
+	u32 units = 0;
+	if (l_seq) {
+		codes[at - 1] = (int8_t)-1;
+		const uintptr_t a = (uintptr_t)(codes + at);
+		units = (u32)((((a + l_seq + 15) & ~(uintptr_t)15) - (a & ~(uintptr_t)15)) >> 4);
+	}
+	u32 tile_units;
+	const u32 unit0 = block_excl_sum<S1_BLOCK / 64, u32>(units, s_tmp, tile_units);
+	s_src[tid] = src;
+	s_len[tid] = l_seq | (rev << 31); /* l_seq < 2^31 */
+	s_at[tid] = at;
+	s_unit0[tid] = unit0;
+	if (tid == 0)
+		s_unit0[S1_BLOCK] = tile_units;
+	__syncthreads();
+	for (u32 u = tid; u < tile_units; u += S1_BLOCK) {
+		u32 lo = 0, hi = S1_BLOCK; /* the record with s_unit0[rec] <= u < s_unit0[rec + 1] */
+#pragma unroll
+		for (int step = 0; step < 8; ++step) {
+			const u32 mid = (lo + hi) >> 1;
+			if (s_unit0[mid] <= u)
+				lo = mid;
+			else
+				hi = mid;
+		}
+		static_assert(S1_BLOCK == 256, "eight halvings");
+		const u32 len = s_len[lo] & 0x7FFFFFFFu;
+		const bool back = (s_len[lo] >> 31) != 0;
+		const u64 rec_at = s_at[lo];
+		int8_t *unit = (int8_t *)((((uintptr_t)(codes + rec_at)) & ~(uintptr_t)15) + 16 * (uintptr_t)(u - s_unit0[lo])); /* 16-byte aligned */
+		const long long j0 = (long long)(unit - (codes + rec_at));                                                       /* the base the unit's first byte holds; < 0 in a record's first unit */
+		const u32 j_lo = j0 < 0 ? 0u : (u32)j0, j_hi = j0 + 16 < (long long)len ? (u32)(j0 + 16) : len;                  /* bases [j_lo, j_hi) */
+		const u32 i_min = back ? len - j_hi : j_lo, i_max = back ? len - 1 - j_lo : j_hi - 1;                            /* as the record stores them */
+		const u32 b0 = i_min >> 1;
+		const u64 p = (u64)s_src[lo] + b0;
+		u64 w = 0;
+		u32 w8 = 0;
+		if (p + 9 <= n) {
+			__builtin_memcpy(&w, text + p, 8);
+			w8 = text[p + 8];
+		} else
+			for (u32 t = 0; t <= (i_max >> 1) - b0; ++t) {
+				const u64 byte = p + t < n ? text[p + t] : 0u;
+				if (t < 8)
+					w |= byte << (8 * t);
+				else
+					w8 = (u32)byte;
+			}
+		int8_t c[16];
+#pragma unroll
+		for (int t = 0; t < 16; ++t) {
+			const long long j = j0 + t;
+			const u32 i = back ? len - 1 - (u32)j : (u32)j;
+			const u32 bi = (i >> 1) - b0;
+			const u32 byte = bi < 8 ? (u32)(w >> (8 * bi)) & 255u : w8;
+			const u32 nib = (i & 1u) ? byte & 15u : byte >> 4;
+			const int code = (nib & (nib - 1u)) == 0 && nib ? __ffs((int)nib) - 1 : -1; /* 1 2 4 8 = A C G T */
+			c[t] = (int8_t)(code < 0 ? -1 : back ? 3 - code : code);
+		}
+		if (j_lo == (u32)j0 && j0 >= 0 && j_hi == (u32)j0 + 16u) {
+			uint4 v;
+			__builtin_memcpy(&v, c, 16);
+			__builtin_memcpy(__builtin_assume_aligned(unit, 16), &v, 16);
+		} else {
+#pragma unroll
+			for (int t = 0; t < 16; ++t)
+				if (j0 + t >= (long long)j_lo && j0 + t < (long long)j_hi)
+					unit[t] = c[t];
+		}
+	}
+}
+
 /* ------------------------------------------------------------------------------------------------ histogram estimate while counting (--opt-out-size)
  * With --opt-out-size the reference hashes every k-mer of every buffer GetSeq returns a second time (CntHashEstimator::Process, called at splitter.cpp:576-577
  * in front of the homopolymer compression) and counts a sample of the hashes in two arrays of 2^r 32-bit counters; stage 2 picks lut_prefix_len from the

@@ -77,6 +77,7 @@ struct HipSplitEngine : KmcSplitEngine {
 	}
 	std::string last_error() override { return err; }
 	bool covers_multiline_fasta() const override { return g_split.ctx && g_split.covers && g_split.covers(2) == 1; }
+	bool covers_bam() const override { return g_split.ctx && g_split.covers && g_split.covers(4) == 1; }
 	/* a library from before the flag ignores it silently: the query is the only way to know */
 	bool covers_homopolymer_compression() const override { return g_split.ctx && g_split.covers && g_split.covers(KMC_HIP_SPLIT_COVERS_HOMOPOLYMER) == 1; }
 	bool covers_histogram_estimation() const override

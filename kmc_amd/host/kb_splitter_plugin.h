@@ -21,10 +21,12 @@
  *
  * FAILS CLOSED (round 5): this worker has no path into the reference's CSplitter. What the engine does not cover stops the run through
  * CCriticalErrorHandler with a message that names it —
- *   per job : input other than FASTA / FASTQ (BAM, KMC; multi-line FASTA unless the engine covers_multiline_fasta()), homopolymer compression (-hc) unless the engine covers_homopolymer_compression(), histogram estimation while counting (--opt-out-size) unless the engine covers_histogram_estimation() (-e alone runs the reference's estimate-only worker, not this one):
+ *   per job : multi-line FASTA unless the engine covers_multiline_fasta(), BAM unless it covers_bam() (a KMC database reaches the splitter as single-line FASTA,
+ *             ">\n<k-mer>\n" per k-mer, binary_reader.h:238-304, and GetSeq treats it as such, splitter.cpp:100: file_type 0), homopolymer compression (-hc) unless the engine covers_homopolymer_compression(), histogram estimation while counting (--opt-out-size) unless the engine covers_histogram_estimation() (-e alone runs the reference's estimate-only worker, not this one):
  *             "use kmc_hip" (the reference's stage 1 + this library's stage 2) is the answer the message gives;
  *   per part: KMC_SPLIT_UNCOVERED — MALFORMED text that CSplitter::GetSeq happens to tolerate (blank lines, a quality string of another length than its
- *             sequence, control characters, a lone '\r').
+ *             sequence, control characters, a lone '\r'); for BAM: records that do not end with the part, a block_size that does not hold its record, a
+ *             read of mem_part_pmm_reads bases or more.
  * Parts the reader labelled ReadType::long_read (queues.h:40) and lines of mem_part_pmm_reads symbols or more go through the engine like any other, and so
  * do the ReadType::na parts of multi-line FASTA (fastq_reader.cpp:399-468, :579-583) with an engine that covers them (file_type 2). With -hc the engine
  * compresses every return of GetSeq on its own, as ProcessReads does (splitter.cpp:575-581); stage 0, the small-k worker and the estimate worker stay the
@@ -144,12 +146,13 @@ class CWSplitter {
 	bool both_strands;
 	uint64 n_reads = 0;
 	/* KMC_HIP_VERBOSE=1: one line per worker on stderr when it finishes */
-	uint64 st_parts = 0, st_long_parts = 0, st_ml_parts = 0, st_uncovered_parts = 0, st_pieces = 0, st_cut_pieces = 0, st_pushes = 0, st_bytes = 0;
+	uint64 st_parts = 0, st_long_parts = 0, st_ml_parts = 0, st_bam_parts = 0, st_uncovered_parts = 0, st_pieces = 0, st_cut_pieces = 0, st_pushes = 0, st_bytes = 0;
 	long long st_engine_ns = 0;
 
-	static const char *uncovered_job(const CKMCParams &P, bool multiline_covered, bool homopolymer_covered, bool estimate_covered)
+	static const char *uncovered_job(const CKMCParams &P, bool multiline_covered, bool homopolymer_covered, bool estimate_covered, bool bam_covered)
 	{
-		if (P.file_type != InputType::FASTA && P.file_type != InputType::FASTQ && !(P.file_type == InputType::MULTILINE_FASTA && multiline_covered))
+		if (P.file_type != InputType::FASTA && P.file_type != InputType::FASTQ && P.file_type != InputType::KMC && !(P.file_type == InputType::MULTILINE_FASTA && multiline_covered) &&
+		    !(P.file_type == InputType::BAM && bam_covered))
 			return "an input format other than FASTA / FASTQ (multi-line FASTA, BAM, KMC)";
 		if (P.homopolymer_compressed && !homopolymer_covered)
 			return "homopolymer compression (-hc)";
@@ -273,7 +276,7 @@ class CWSplitter {
 		sp.n_bins = Params.n_bins;
 		sp.max_x = Params.max_x;
 		sp.both_strands = Params.both_strands ? 1 : 0;
-		sp.file_type = Params.file_type == InputType::FASTQ ? 1 : Params.file_type == InputType::MULTILINE_FASTA ? 2 : 0;
+		sp.file_type = Params.file_type == InputType::FASTQ ? 1 : Params.file_type == InputType::MULTILINE_FASTA ? 2 : Params.file_type == InputType::BAM ? 4 : 0; /* KMC: 0 */
 		sp.line_cap = (uint64_t)Params.mem_part_pmm_reads;
 		sp.sig_to_bin = Queues.s_mapper->GetMap();
 		sp.homopolymer_compressed = Params.homopolymer_compressed ? 1 : 0;
@@ -299,10 +302,10 @@ public:
 		max_x = Params.max_x;
 		both_strands = Params.both_strands;
 		buffer_size = Params.bin_part_size;
-		if (Params.file_type == InputType::MULTILINE_FASTA || Params.homopolymer_compressed || estimating(Params, Queues))
+		if (Params.file_type == InputType::MULTILINE_FASTA || Params.file_type == InputType::BAM || Params.homopolymer_compressed || estimating(Params, Queues))
 			engine.reset(make_engine(Params, Queues)); /* whether the format / the compression / the estimate is covered is the engine's answer */
 		if (const char *what = uncovered_job(Params, engine && engine->covers_multiline_fasta(), engine && engine->covers_homopolymer_compression(),
-		                                     engine && engine->covers_histogram_estimation())) {
+		                                     engine && engine->covers_histogram_estimation(), engine && engine->covers_bam())) {
 #ifdef KMC_HIP_S1_REFERENCE_FALLBACK
 			const char *fb = getenv("KMC_HIP_S1_FALLBACK");
 			if (fb && fb[0] == '1') {
@@ -356,13 +359,14 @@ public:
 			ReadType read_type;
 			if (!pq->pop(part, size, read_type))
 				continue;
-			/* only the multi-line FASTA reader makes ReadType::na parts (fastq_reader.cpp:399-468, :579-583); the constructor took that format only
-			 * from an engine that covers it, and the engine was made with file_type 2 */
-			if (read_type == ReadType::na && params->file_type != InputType::MULTILINE_FASTA)
+			/* only the multi-line FASTA reader (fastq_reader.cpp:399-468, :579-583) and the BAM readers (:191-362) make ReadType::na parts; the constructor
+			 * took those formats only from an engine that covers them, and the engine was made with file_type 2 / 4 */
+			if (read_type == ReadType::na && params->file_type != InputType::MULTILINE_FASTA && params->file_type != InputType::BAM)
 				CCriticalErrorHandler::Inst().HandleCriticalError("Error: stage 1 on the device got a part of ReadType::na");
 			const bool long_read = read_type == ReadType::long_read;
 			st_long_parts += long_read ? 1 : 0;
-			st_ml_parts += read_type == ReadType::na ? 1 : 0;
+			st_ml_parts += read_type == ReadType::na && params->file_type != InputType::BAM ? 1 : 0;
+			st_bam_parts += read_type == ReadType::na && params->file_type == InputType::BAM ? 1 : 0;
 			KmcSplitResult r;
 			const auto t0 = std::chrono::steady_clock::now();
 			const int rc = engine->split_part(part, size, long_read, r);
@@ -375,6 +379,11 @@ public:
 					continue;
 				}
 #endif
+				if (params->file_type == InputType::BAM)
+					CCriticalErrorHandler::Inst().HandleCriticalError(
+					    "Error: stage 1 on the device: a part of the BAM input is not covered: its alignment records do not end exactly at the end of the part, a "
+					    "block_size is smaller than its record's header, name, cigar, bases and qualities (or negative), or a read that is counted has "
+					    "mem_part_pmm_reads bases or more. Run this input with kmc_hip (the reference's stage 1, stage 2 on the device).");
 				if (read_type == ReadType::na)
 					CCriticalErrorHandler::Inst().HandleCriticalError(
 					    "Error: stage 1 on the device: a part of the multi-line FASTA input ends inside a title line (a title longer than the reader's part). "
@@ -404,10 +413,10 @@ public:
 		KmcTimeline::mark_first_last(nullptr, "splitter: last worker done");
 		if (getenv("KMC_HIP_VERBOSE"))
 			fprintf(stderr, "[kmc_hip stage 1] worker: %llu parts through the engine (%.3f s inside; %llu of them long-read parts), %llu uncovered parts, "
-			                "%llu bin pieces (%llu cut record by record), %llu buffers / %.1f MB pushed, %llu multi-line FASTA parts%s\n",
+			                "%llu bin pieces (%llu cut record by record), %llu buffers / %.1f MB pushed, %llu multi-line FASTA parts, %llu BAM parts%s\n",
 			        (unsigned long long)st_parts, st_engine_ns * 1e-9, (unsigned long long)st_long_parts, (unsigned long long)st_uncovered_parts,
 			        (unsigned long long)st_pieces,
-			        (unsigned long long)st_cut_pieces, (unsigned long long)st_pushes, st_bytes / 1e6, (unsigned long long)st_ml_parts,
+			        (unsigned long long)st_cut_pieces, (unsigned long long)st_pushes, st_bytes / 1e6, (unsigned long long)st_ml_parts, (unsigned long long)st_bam_parts,
 			        params->homopolymer_compressed ? ", homopolymer-compressed (-hc) on the device" : "");
 	}
 

@@ -20,7 +20,8 @@
 struct KmcSplitParams {
 	uint32_t kmer_len, signature_len, n_bins, max_x;
 	int both_strands;
-	int file_type;             /* 0 = FASTA (one line per sequence), 1 = FASTQ, 2 = multi-line FASTA (ReadType::na parts; only for an engine that covers_multiline_fasta()) */
+	int file_type;             /* 0 = FASTA (one line per sequence), 1 = FASTQ, 2 = multi-line FASTA (ReadType::na parts; only for an engine that covers_multiline_fasta()),
+	                            * 4 = BAM alignment records (ReadType::na parts, GetSeq splitter.cpp:326-419; only for an engine that covers_bam()) */
 	uint64_t line_cap;         /* mem_part_pmm_reads: longer lines are cut into pieces overlapping by kmer_len - 1 symbols (splitter.cpp:141-145) */
 	const int32_t *sig_to_bin; /* CSignatureMapper's map, 4^signature_len + 1 entries (s_mapper.h:232) */
 	int homopolymer_compressed = 0; /* -hc: every return of GetSeq is compressed on its own (splitter.cpp:424-435, :575-581); only for an engine that
@@ -49,6 +50,8 @@ struct KmcSplitEngine {
 	virtual std::string last_error() = 0;
 	/* parts of multi-line FASTA (file_type 2: CFastqReader::GetPartFromMultilneFasta, split as CSplitter::GetSeq's MULTILINE_FASTA branch) */
 	virtual bool covers_multiline_fasta() const { return false; }
+	/* parts of BAM records (file_type 4: whole records as the reference's BAM readers hand them out, fastq_reader.cpp:191-362) */
+	virtual bool covers_bam() const { return false; }
 	/* -hc (KmcSplitParams::homopolymer_compressed), with every file type and with long-read parts */
 	virtual bool covers_homopolymer_compression() const { return false; }
 	/* histogram estimation while counting (--opt-out-size; KmcSplitParams::estimate_s / _r): the engine keeps the two counter arrays of CntHashEstimator

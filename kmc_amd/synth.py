@@ -155,6 +155,85 @@ def make_long_reads(path: str, seed: int, read_lens, fmt: str = "fq", mean_run: 
     return total
 
 
+# ---- BAM (the input of -fbam), written with struct and zlib alone
+_BAM_NIBBLE_OF = np.full(256, 255, dtype=np.uint8)
+_BAM_NIBBLE_OF[np.frombuffer(b"=ACMGRSVTWYHKDBN", dtype=np.uint8)] = np.arange(16, dtype=np.uint8)
+_TO_ACGTN = bytes(c if c in b"ACGT" else ord("N") for c in range(256))
+_TO_COMPLEMENT = bytes({65: 84, 67: 71, 71: 67, 84: 65}.get(c, ord("N")) for c in range(256))
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bam_record(seq, flag: int = 0, name: bytes = b"r", n_cigar: int = 0, qual: bool = True, tags: bytes = b"", pad_to: int = 0) -> bytes:
+    """One BAM alignment record (block_size included). `seq`: a str over "=ACMGRSVTWYHKDBN" as the record STORES it (an aligner stores a reversed read
+    reverse-complemented and sets flag 0x10), or a sequence of nibble values 0..15; first base in the high nibble. `name` without its NUL (l_read_name = len + 1,
+    at most 254 bytes); `n_cigar` operations "1M"; qualities 0xFF * l_seq (none with qual=False: not a legal record, a block_size the device refuses); `tags`
+    raw bytes behind the qualities, grown with filler to make the whole record `pad_to` bytes when that is larger."""
+    import struct
+
+    nib = _BAM_NIBBLE_OF[np.frombuffer(seq.encode(), dtype=np.uint8)] if isinstance(seq, str) else np.asarray(seq, dtype=np.uint8) & 15
+    assert int(nib.max(initial=0)) < 16, "a base outside =ACMGRSVTWYHKDBN"
+    l_seq = int(nib.size)
+    even = np.zeros(l_seq + (l_seq & 1), dtype=np.uint8)
+    even[:l_seq] = nib
+    packed = ((even[0::2] << 4) | even[1::2]).tobytes()
+    body = name + b"\0" + struct.pack("<I", (1 << 4) | 0) * n_cigar + packed + (b"\xff" * l_seq if qual else b"")
+    fixed = 36 + len(body) + len(tags)
+    tags = tags + b"\x5a" * max(0, pad_to - fixed)
+    block_size = 32 + len(body) + len(tags)
+    head = struct.pack("<iiiIIiiii", block_size, -1, -1, (4680 << 16) | (len(name) + 1), ((flag & 0xFFFF) << 16) | n_cigar, l_seq, -1, -1, 0)
+    return head + body + tags
+
+
+def bam_part(records) -> bytes:
+    """A part as the reference's BAM readers hand it to the splitter: whole records, one after the other, nothing else."""
+    return b"".join(records)
+
+
+def bgzf_blocks(data: bytes, block_bytes: int = 0xFF00, level: int = 6) -> bytes:
+    """`data` as BGZF members of `block_bytes` uncompressed bytes each (gzip with the BC extra field that holds BSIZE, raw deflate, CRC32, ISIZE), without
+    the EOF block."""
+    import struct
+    import zlib
+
+    out = bytearray()
+    for lo in range(0, len(data), block_bytes):
+        chunk = data[lo:lo + block_bytes]
+        z = zlib.compressobj(level, zlib.DEFLATED, -15)
+        comp = z.compress(chunk) + z.flush()
+        bsize = 12 + 6 + len(comp) + 8
+        assert bsize <= 0x10000
+        out += struct.pack("<4BI2BH2BHH", 0x1F, 0x8B, 8, 4, 0, 0, 0xFF, 6, 0x42, 0x43, 2, bsize - 1) + comp + struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk))
+    return bytes(out)
+
+
+def write_bam(path: str, records, block_bytes: int = 3000, text: bytes = b"@HD\tVN:1.6\tSO:unsorted\n", refs=()) -> int:
+    """Write an (unaligned-style) BAM file: header (magic, l_text, text, n_ref, references as (name, length)) and `records` (bam_record) as one BGZF
+    stream cut every `block_bytes` uncompressed bytes WITHOUT regard to record boundaries — records span blocks, as in files samtools writes — and the
+    28-byte EOF block. Returns bytes written."""
+    import struct
+
+    head = b"BAM\1" + struct.pack("<i", len(text)) + text + struct.pack("<i", len(refs))
+    for name, length in refs:
+        head += struct.pack("<i", len(name) + 1) + name + b"\0" + struct.pack("<i", length)
+    blob = bgzf_blocks(head + b"".join(records), block_bytes) + BGZF_EOF
+    with open(path, "wb") as f:
+        f.write(blob)
+    return len(blob)
+
+
+def bam_reads_as_getseq(reads, both_strands: bool):
+    """What CSplitter::GetSeq's BAM branch (splitter.cpp:326-419) returns for records given as (seq str, flag): the included sequences, in order, as ASCII with
+    N for every base that is not A C G T, reversed and complemented where flag 0x10 is set and both_strands is off; and the number of included records."""
+    out, n = [], 0
+    for seq, flag in reads:
+        if flag & 0x900:
+            continue
+        n += 1
+        raw = seq.encode()
+        out.append(raw[::-1].translate(_TO_COMPLEMENT) if not both_strands and flag & 0x10 else raw.translate(_TO_ACGTN))
+    return out, n
+
+
 # Named configurations of BASELINE.json / SURVEY.md §8d
 CONFIGS = {
     "C1": dict(seed=12345, genome_len=400_000, n_reads=33_000),          # 10 MB FASTQ plumbing case
