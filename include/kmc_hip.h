@@ -355,6 +355,7 @@ int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, 
  * from before the flag answers 0, like for every value it does not know). */
 #define KMC_HIP_SPLIT_COVERS_HOMOPOLYMER 0x100u
 #define KMC_HIP_SPLIT_COVERS_ESTIMATE 0x102u /* KMC_HIP_SPLIT_ESTIMATE and kmc_hip_estimate_open / _read / _close (0x101 stays unknown) */
+#define KMC_HIP_SPLIT_COVERS_SMALLK 0x103u   /* kmc_hip_smallk_open / _part / _read / _close: small k (k <= 13) counted on the device */
 int kmc_hip_split_covers(uint32_t what);
 int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint8_t *recs,
                        uint64_t recs_capacity, uint64_t *recs_bytes, uint64_t *bin_off, uint64_t *bin_bytes, uint64_t *bin_kmers, uint64_t *bin_superkmers, uint64_t *bin_plus_x,
@@ -374,6 +375,31 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 int kmc_hip_estimate_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t s, uint32_t r);
 int kmc_hip_estimate_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint32_t *dst);
 int kmc_hip_estimate_close(kmc_hip_ctx *ctx, int dev);
+
+/* ---- stage 1, small k (k <= 13; added within ABI version 4, like kmc_hip_estimate_*) ----
+ * With k <= 13 the reference counts without signatures and bins whenever the tables fit in memory, and always when k < signature_len ("small k optimization",
+ * CKMC::AdjustMemoryLimitsSmallK kmc.h:677-750): every CWSmallKSplitter worker (splitter.h:138, splitter.cpp:929-983) keeps one table of 4^k counters that
+ * CSplitter::ProcessReadsSmallK (splitter.cpp:682-805) increments once per k-mer, and stage 2 (ProcessSmallKOptimization_Stage2 kmc.h:865-960, CSmallKCompleter)
+ * sums the workers' tables and writes the database. These entries keep ONE such table on `dev` (k_s1_smallk_count); the caller hands it to the reference's
+ * stage 2 as one worker's table. Ask kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_SMALLK) first.
+ * _open : replaces the reserve + memset of CWSmallKSplitter::operator() (splitter.cpp:954-955): allocates and zeroes 4^kmer_len uint64 counters (8 bytes at
+ *         k = 1, 512 MB at k = 13); kmer_len 1..13. Opening again with the same (kmer_len, both_strands) is a no-op, with another pair KMC_HIP_EINVAL.
+ * _part : replaces CSplitter::ProcessReadsSmallK for one part (splitter.cpp:682-805, with GetSeq :88-421 and HomopolymerCompressSeq :424-435 in front): every
+ *         window of k valid symbols of every buffer GetSeq returns (compressed first with KMC_HIP_SPLIT_HOMOPOLYMER) adds one to its k-mer's counter — the
+ *         canonical k-mer, min(forward, reverse complement) as 2k-bit integers, with both_strands, the forward one without. Uses kmer_len, both_strands,
+ *         file_type (0, 1, 2, 4), line_cap (mem_part_pmm_reads; (MAX_LINE_SIZE + 1) * 8 in this mode, kmc.h:689), part_kind and flags (only
+ *         KMC_HIP_SPLIT_HOMOPOLYMER; any other bit is KMC_HIP_EINVAL) of `p`; signature_len, n_bins and max_x are ignored and no signature map is needed.
+ *         *n_reads = titles in the part (as kmc_hip_split_part), *n_kmers = the windows counted (CSplitter::total_kmers :751, :799). Returns 0, a negative
+ *         code, or KMC_HIP_UNCOVERED for the malformed inputs kmc_hip_split_part answers it for. A call that does not return 0 leaves the table as it was: the
+ *         counting kernel is launched only once the call can no longer fail. Calls on different slots of one device may run at once and add into the one table.
+ * _read : replaces CWSmallKSplitter::GetResult (splitter.h:155-158): waits for everything the device's slots have launched, then copies entries
+ *         [first, first + count) to dst, so that a caller can drain in chunks. The table is not cleared.
+ * _close: replaces CWSmallKSplitter::Release (splitter.h:167-170): frees the table (kmc_hip_destroy does it too); none open is not an error. It waits for the
+ *         kmc_hip_smallk_part calls that are inside the library on `dev`; a call that starts after it finds no table (KMC_HIP_EINVAL). */
+int kmc_hip_smallk_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t both_strands);
+int kmc_hip_smallk_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint64_t *n_reads, uint64_t *n_kmers);
+int kmc_hip_smallk_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint64_t *dst);
+int kmc_hip_smallk_close(kmc_hip_ctx *ctx, int dev);
 
 #ifdef __cplusplus
 }

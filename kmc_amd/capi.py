@@ -81,6 +81,8 @@ SPLIT_FILE_BAM = 4  # kmc_hip_split_params.file_type: a part of BAM alignment re
 SPLIT_HOMOPOLYMER = 1  # KMC_HIP_SPLIT_HOMOPOLYMER: flags bit 0, -hc
 SPLIT_ESTIMATE = 4  # KMC_HIP_SPLIT_ESTIMATE: flags bit 2, --opt-out-size (the part's k-mers go to the estimator of kmc_hip_estimate_open)
 SPLIT_COVERS_ESTIMATE = 0x102  # KMC_HIP_SPLIT_COVERS_ESTIMATE
+SPLIT_COVERS_SMALLK = 0x103  # KMC_HIP_SPLIT_COVERS_SMALLK: kmc_hip_smallk_open / _part / _read / _close (k <= 13 counted on the device)
+SMALLK_MAX_K = 13
 SPLIT_COVERS_HOMOPOLYMER = 0x100  # KMC_HIP_SPLIT_COVERS_HOMOPOLYMER: ask kmc_hip_split_covers before setting the flag (an older library ignores it)
 
 
@@ -103,6 +105,7 @@ SYMBOLS = [
     "kmc_hip_debug_expand", "kmc_hip_debug_compact", "kmc_hip_debug_split_reads",
     "kmc_hip_split_reads_plan", "kmc_hip_split_reads_emit", "kmc_hip_split_reads_free",
     "kmc_hip_split_set_map", "kmc_hip_split_part", "kmc_hip_split_covers", "kmc_hip_estimate_open", "kmc_hip_estimate_read", "kmc_hip_estimate_close",
+    "kmc_hip_smallk_open", "kmc_hip_smallk_part", "kmc_hip_smallk_read", "kmc_hip_smallk_close",
 ]
 
 _LIB = None
@@ -187,6 +190,11 @@ def load():
         L.kmc_hip_estimate_open.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]
         L.kmc_hip_estimate_read.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp]
         L.kmc_hip_estimate_close.argtypes = [vp, C.c_int]
+    if hasattr(L, "kmc_hip_smallk_open"):  # added within ABI version 4: ask kmc_hip_split_covers(SPLIT_COVERS_SMALLK)
+        L.kmc_hip_smallk_open.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32]
+        L.kmc_hip_smallk_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(SplitParams), vp, C.c_uint64, u64p, u64p]
+        L.kmc_hip_smallk_read.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp]
+        L.kmc_hip_smallk_close.argtypes = [vp, C.c_int]
     _LIB = L
     return L
 

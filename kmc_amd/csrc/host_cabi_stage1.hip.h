@@ -347,7 +347,10 @@ int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, 
 	return 0;
 }
 
-int kmc_hip_split_covers(uint32_t what) { return what <= 2 || what == 4 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER || what == KMC_HIP_SPLIT_COVERS_ESTIMATE ? 1 : 0; }
+int kmc_hip_split_covers(uint32_t what)
+{
+	return what <= 2 || what == 4 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER || what == KMC_HIP_SPLIT_COVERS_ESTIMATE || what == KMC_HIP_SPLIT_COVERS_SMALLK ? 1 : 0;
+}
 
 /* ---- histogram estimation while counting (--opt-out-size): the device's share of the reference's CntHashEstimator counters ---- */
 int kmc_hip_estimate_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t s, uint32_t r)
@@ -546,6 +549,176 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 		bin_kmers[b] = R.bin_kmers[b];
 		bin_superkmers[b] = R.bin_sk[b];
 		bin_plus_x[b] = R.bin_plus_x[b];
+	}
+	*n_reads = R.n_reads;
+	return 0;
+}
+
+/* ---- small k (k <= 13) on the device: the one table the reference's small-k stage 2 reads (CSplitter::ProcessReadsSmallK, splitter.cpp:682-805) ---- */
+int kmc_hip_smallk_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t both_strands)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	if (kmer_len < 1 || kmer_len > S1_SMALLK_MAX_K)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_open: kmer_len 1..13");
+	Dev &d = *ctx->devs[dev];
+	std::lock_guard<std::mutex> lck(d.smallk_mtx);
+	if (d.d_smallk) {
+		if (d.smallk_k == kmer_len && d.smallk_both == (both_strands ? 1u : 0u))
+			return 0;
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_open: a table with another kmer_len / both_strands is open on this device");
+	}
+	const size_t bytes = ((size_t)1 << (2 * kmer_len)) * sizeof(u64);
+	u64 *p = nullptr;
+	HIPCHK(hipMalloc((void **)&p, bytes));
+	hipError_t e = hipMemset(p, 0, bytes);
+	if (e == hipSuccess)
+		e = hipDeviceSynchronize();
+	if (e != hipSuccess) {
+		(void)hipFree(p);
+		return fail_hip("hipMemset(small-k table)", e);
+	}
+	d.d_smallk = p;
+	d.smallk_k = kmer_len, d.smallk_both = both_strands ? 1u : 0u;
+	return 0;
+}
+
+int kmc_hip_smallk_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint64_t *dst)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	Dev &d = *ctx->devs[dev];
+	std::lock_guard<std::mutex> lck(d.smallk_mtx);
+	if (!d.d_smallk)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_read: no small-k table is open on this device");
+	const uint64_t entries = (uint64_t)1 << (2 * d.smallk_k);
+	if ((count && !dst) || first > entries || count > entries - first)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_read: [first, first + count) lies outside the 4^k entries");
+	if (int rc = estimate_wait_slots(d))
+		return rc;
+	if (count)
+		HIPCHK(hipMemcpy(dst, d.d_smallk + first, (size_t)count * sizeof(u64), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int kmc_hip_smallk_close(kmc_hip_ctx *ctx, int dev)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	Dev &d = *ctx->devs[dev];
+	std::unique_lock<std::mutex> lck(d.smallk_mtx);
+	/* a kmc_hip_smallk_part call holds d_smallk from its check to its return, without the mutex: the table outlives every such call */
+	d.smallk_idle.wait(lck, [&d] { return d.smallk_users == 0; });
+	if (!d.d_smallk)
+		return 0;
+	if (int rc = estimate_wait_slots(d))
+		return rc;
+	HIPCHK(hipFree(d.d_smallk));
+	d.d_smallk = nullptr;
+	d.smallk_k = d.smallk_both = 0;
+	return 0;
+}
+
+int kmc_hip_smallk_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint64_t *n_reads, uint64_t *n_kmers)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	if (!p || (size && !text) || !n_reads || !n_kmers || slot < 0 || slot >= N_SLOTS)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: bad argument");
+	if (p->kmer_len < 1 || p->kmer_len > S1_SMALLK_MAX_K || p->file_type > 4 || p->file_type == 3 || p->part_kind > 1)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: unsupported parameters (kmer_len 1..13, file_type 0, 1, 2 or 4, part_kind 0 or 1)");
+	if (p->flags & ~KMC_HIP_SPLIT_HOMOPOLYMER)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: unknown bit in flags (KMC_HIP_SPLIT_ESTIMATE included: the reference refuses it with small k, kmc.h:773-779)");
+	if ((p->file_type == 2 || p->file_type == 4) && p->part_kind != 0)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: a part of multi-line FASTA (file_type 2) or of BAM records (file_type 4) is a ReadType::na part: part_kind must be 0");
+	if (p->file_type == 4 && size >= S1_BAM_MAX_PART)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: a part of BAM records (file_type 4) must be smaller than 2 GiB");
+	if (p->line_cap < (uint64_t)p->kmer_len + S1_WG_TILE + 2)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: line_cap (mem_part_pmm_reads) is too small for the device splitter: it needs kmer_len + " + std::to_string(S1_WG_TILE + 2) +
+		                                " symbols at least");
+	Dev &d = *ctx->devs[dev];
+	u64 *d_table = nullptr;
+	struct TableUser { /* counted from here to the call's return, so that a concurrent kmc_hip_smallk_close cannot free the table in front of the kernel */
+		Dev *d = nullptr;
+		~TableUser()
+		{
+			if (!d)
+				return;
+			std::lock_guard<std::mutex> lck(d->smallk_mtx);
+			if (--d->smallk_users == 0)
+				d->smallk_idle.notify_all();
+		}
+	} table_user;
+	{
+		std::lock_guard<std::mutex> lck(d.smallk_mtx);
+		if (!d.d_smallk)
+			return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part without kmc_hip_smallk_open on this device");
+		if (d.smallk_k != p->kmer_len || d.smallk_both != (p->both_strands ? 1u : 0u))
+			return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: the open table has another kmer_len / both_strands");
+		d_table = d.d_smallk;
+		++d.smallk_users;
+		table_user.d = &d;
+	}
+	*n_reads = *n_kmers = 0;
+	Slot &s = d.slot[slot];
+	std::lock_guard<std::mutex> lck(s.mtx);
+	/* the front half's share of kmc_hip_split_part's work area: text + codes + line ends (multi-line FASTA: sequence starts) + the -hc stream; BAM: two bases per byte */
+	const bool hc = (p->flags & KMC_HIP_SPLIT_HOMOPOLYMER) != 0;
+	const size_t per_byte = p->file_type == 4 ? 8 + (hc ? 4 : 0) : (p->file_type == 2 ? 8 : 6) + (hc ? 2 : 0);
+	if (int rc = ensure(d.s1_arena[slot], (size_t)size * per_byte + ((size_t)32 << 20)))
+		return rc;
+	S1HipBackend be;
+	be.stream = s.stream;
+	be.slot = &s;
+	be.arena = &d.s1_arena[slot];
+	S1PartParams sp;
+	sp.k = p->kmer_len;
+	sp.m = 0, sp.n_bins = 0, sp.max_x = 0; /* the bin path's: not read by the front half */
+	sp.both_strands = p->both_strands ? 1u : 0u;
+	sp.lines_per_record = p->file_type == 1 ? 4u : 2u;
+	sp.multiline_fasta = p->file_type == 2;
+	sp.bam = p->file_type == 4;
+	sp.homopolymer = hc;
+	sp.line_cap = p->line_cap;
+	sp.d_sig_to_bin = nullptr;
+	u32 max_wgs = S1_SMALLK_WGS, lds_k = S1_SMALLK_LDS_K; /* measurement and test switches, like KMC_HIP_S1_SORTED_EMIT: the result does not depend on them */
+	if (const char *e = getenv("KMC_HIP_S1_SMALLK_WGS"))
+		max_wgs = (u32)atoi(e) > 0 ? (u32)atoi(e) : max_wgs;
+	if (const char *e = getenv("KMC_HIP_S1_SMALLK_LDS_K"))
+		lds_k = (u32)atoi(e) <= S1_SMALLK_LDS_K ? (u32)atoi(e) : lds_k;
+	S1PartResult R;
+	S1Front F;
+	u64 long_reads = 0;
+	if (p->part_kind == 1) {
+		const u64 skip = s1_long_read_title(text, size, p->file_type, long_reads);
+		text += skip;
+		size -= skip;
+		sp.lines_per_record = 0;
+	}
+	try {
+		uint8_t *d_text = (uint8_t *)be.alloc(size + 16);
+		if (size) {
+			hipError_t e = hipMemcpyAsync(d_text, text, size, hipMemcpyHostToDevice, s.stream);
+			if (e != hipSuccess)
+				return fail_hip("hipMemcpyAsync(text)", e);
+		}
+		const int rc = s1_front_part(be, d_text, size, size && text[size - 1] == '\n', sp, R, F, true);
+		if (p->part_kind == 1)
+			R.n_reads = long_reads;
+		if (rc == S1_CHAIN_UNCOVERED)
+			return KMC_HIP_UNCOVERED;
+		if (rc != S1_CHAIN_OK)
+			return R.device_error ? err_to_code(R.device_error) : fail(KMC_HIP_EDEVICE, "kmc_hip_smallk_part: stage-1 chain failed");
+		/* nothing below fails because of the part: only now may its k-mers reach the table */
+		u64 counted = 0;
+		if (F.n >= p->kmer_len) {
+			u64 *d_total = (u64 *)be.alloc(8);
+			s1_smallk_part(be, (const int8_t *)F.d_codes, F.n, p->kmer_len, sp.both_strands, d_table, d_total, max_wgs, lds_k);
+			be.d2h(&counted, d_total, 8);
+		}
+		*n_kmers = counted;
+	} catch (const S1BackendFailure &f) {
+		return fail_hip(f.what, f.e);
 	}
 	*n_reads = R.n_reads;
 	return 0;

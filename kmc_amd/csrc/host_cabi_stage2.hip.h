@@ -177,6 +177,8 @@ void kmc_hip_destroy(kmc_hip_ctx *ctx)
 			(void)hipFree(d->d_sig_map);
 		if (d->d_est)
 			(void)hipFree(d->d_est);
+		if (d->d_smallk)
+			(void)hipFree(d->d_smallk);
 		for (auto &a : d->s1_arena)
 			if (a.p)
 				(void)hipFree(a.p);

@@ -250,6 +250,11 @@ struct Dev {
 	u32 est_users = 0; /* kmc_hip_split_part calls that took d_est and have not returned: kmc_hip_estimate_close waits for them */
 	std::mutex est_mtx;
 	std::condition_variable est_idle;
+	u64 *d_smallk = nullptr; /* stage 1, small k: the 4^smallk_k counters of kmc_hip_smallk_open; nullptr = none open */
+	u32 smallk_k = 0, smallk_both = 0;
+	u32 smallk_users = 0; /* kmc_hip_smallk_part calls that took d_smallk and have not returned: kmc_hip_smallk_close waits for them */
+	std::mutex smallk_mtx;
+	std::condition_variable smallk_idle;
 };
 
 u32 counter_bytes(u64 cutoff_max, u64 counter_max) { return kmc_counter_bytes(cutoff_max, counter_max); }

@@ -65,15 +65,25 @@ static inline u64 s1_long_read_title(const uint8_t *text, u64 size, u32 file_typ
 	return p;
 }
 
-template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, bool text_ends_with_newline, const S1PartParams &P, S1PartResult &R)
+/* What the front half of the chain leaves behind for whoever goes on with the codes: the stream that is cut / counted (the -hc stream with -hc), the small
+ * block and the words in it. R.d_raw_codes / n_raw, n_reads and n_symbols are set as well. */
+struct S1Front {
+	u64 *d_small = nullptr, *d_has_marks = nullptr;
+	u32 *d_ticket = nullptr, *d_err = nullptr;
+	const u64 *d_cut_marks = nullptr; /* nullptr: no code of d_codes carries S1_PIECE_MARK (the -hc stream: pieces are sequences of their own) */
+	int8_t *d_codes = nullptr;
+	u64 n = 0;
+};
+
+/* The front half: text / BAM records / multi-line FASTA -> codes, piece marks, the record check, the -hc compaction, n_reads and n_symbols; the part's error
+ * words -> S1_CHAIN_UNCOVERED. Uses of P: k, both_strands, lines_per_record, line_cap and the format switches, nothing of the bin path (m, n_bins, max_x, the map).
+ * wait_for_errors: without -hc the record check runs beside whatever the caller launches next and its error word is read with that (the bin path: beside the
+ * cut); a caller with nothing to launch that may fail (s1_smallk_part) waits for it here, so that S1_CHAIN_OK means the codes are those of a covered part. */
+template <class B> int s1_front_part(B &be, const uint8_t *d_text, u64 size, bool text_ends_with_newline, const S1PartParams &P, S1PartResult &R, S1Front &F, bool wait_for_errors)
 {
-	const u32 nb = P.n_bins, lpr = P.lines_per_record;
+	const u32 lpr = P.lines_per_record;
 	R = S1PartResult();
-	R.bin_off.assign(nb, 0);
-	R.bin_bytes.assign(nb, 0);
-	R.bin_sk.assign(nb, 0);
-	R.bin_kmers.assign(nb, 0);
-	R.bin_plus_x.assign(nb, 0);
+	F = S1Front();
 	if (!size)
 		return S1_CHAIN_OK;
 	/* small block: [0] '\\n' count | [1] code bytes | [2] super-k-mers | [3] lo: ticket, hi: error word | [4] != 0: some code carries S1_PIECE_MARK |
@@ -201,6 +211,41 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 		n = hc[2];
 		d_cut_marks = nullptr;
 	}
+	F.d_small = d_small, F.d_has_marks = d_has_marks, F.d_ticket = d_ticket, F.d_err = d_err;
+	F.d_cut_marks = d_cut_marks, F.d_codes = d_codes, F.n = n;
+	if (wait_for_errors && !(P.homopolymer && n)) { /* the -hc block has just read the word */
+		if (!be.d2h(small, d_small, sizeof small))
+			return S1_CHAIN_BACKEND_FAILURE;
+		err = (u32)(small[3] >> 32);
+		if (err & S1_TEXT_BAD)
+			return S1_CHAIN_UNCOVERED;
+		if (err) {
+			R.device_error = err;
+			return S1_CHAIN_DEVICE_ERROR;
+		}
+	}
+	return S1_CHAIN_OK;
+}
+
+template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, bool text_ends_with_newline, const S1PartParams &P, S1PartResult &R)
+{
+	const u32 nb = P.n_bins;
+	S1Front F;
+	const int front = s1_front_part(be, d_text, size, text_ends_with_newline, P, R, F, false);
+	R.bin_off.assign(nb, 0);
+	R.bin_bytes.assign(nb, 0);
+	R.bin_sk.assign(nb, 0);
+	R.bin_kmers.assign(nb, 0);
+	R.bin_plus_x.assign(nb, 0);
+	if (front != S1_CHAIN_OK || !size)
+		return front;
+	u64 *const d_small = F.d_small;
+	u32 *const d_ticket = F.d_ticket, *const d_err = F.d_err;
+	const u64 *const d_cut_marks = F.d_cut_marks;
+	const int8_t *const d_codes = F.d_codes;
+	const u64 n = F.n;
+	u64 small[4];
+	u32 err;
 	/* ---- codes -> super-k-mers. Their number is only known afterwards: a guess, and a second cut with the exact number when it was short. */
 	u64 n_sk = 0, cap = n / P.sk_guess_div + 4096;
 	u64 *d_pos = nullptr;
@@ -315,6 +360,27 @@ template <class B> void s1_estimate_part(B &be, const int8_t *d_raw_codes, u64 n
 	if (n < k)
 		return;
 	S1_LAUNCH(B, be, k_s1_nthash_estimate, dim3((u32)((n + S1_TXT_TILE - 1) / S1_TXT_TILE)), dim3(S1_BLOCK), d_raw_codes, n, k, s, r, s1_nt_seeds(k), d_counters);
+}
+
+/* Small k (k <= 13, the reference's "small k optimization", CSplitter::ProcessReadsSmallK splitter.cpp:682-805): every window of k valid codes of the stream
+ * the front half leaves (S1Front::d_codes, n: the raw stream, or the -hc stream with -hc) is one k-mer, counted in the table of 4^k 64-bit counters at
+ * d_table; *d_total (zeroed by the caller) receives the number of windows. Like s1_estimate_part the caller launches this once nothing can fail any more.
+ * Workgroups are persistent over tiles: max_wgs of them at most, and never more than S1_SMALLK_MAX_TILES_PER_WG tiles each (their 32-bit LDS counters).
+ * lds_k: the largest k whose table is kept in LDS (S1_SMALLK_LDS_K; 0 = every k adds straight into d_table). */
+template <class B> void s1_smallk_part(B &be, const int8_t *d_codes, u64 n, u32 k, u32 both_strands, u64 *d_table, u64 *d_total, u32 max_wgs = S1_SMALLK_WGS, u32 lds_k = S1_SMALLK_LDS_K)
+{
+	if (n < k)
+		return;
+	const u64 tiles = (n + S1_TXT_TILE - 1) / S1_TXT_TILE, least = (tiles + S1_SMALLK_MAX_TILES_PER_WG - 1) / S1_SMALLK_MAX_TILES_PER_WG;
+	u64 grid = tiles < max_wgs ? tiles : (max_wgs ? max_wgs : 1);
+	if (grid < least)
+		grid = least;
+	if (k <= lds_k && k <= 6)
+		S1_LAUNCH(B, be, (k_s1_smallk_count<6>), dim3((u32)grid), dim3(S1_BLOCK), d_codes, n, k, both_strands, d_table, d_total);
+	else if (k <= lds_k && k == 7)
+		S1_LAUNCH(B, be, (k_s1_smallk_count<7>), dim3((u32)grid), dim3(S1_BLOCK), d_codes, n, k, both_strands, d_table, d_total);
+	else
+		S1_LAUNCH(B, be, (k_s1_smallk_count<0>), dim3((u32)grid), dim3(S1_BLOCK), d_codes, n, k, both_strands, d_table, d_total);
 }
 
 #endif

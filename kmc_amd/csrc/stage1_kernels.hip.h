@@ -1482,6 +1482,139 @@ __global__ void __launch_bounds__(S1_BLOCK) k_s1_nthash_estimate(const int8_t *_
 	}
 }
 
+/* ------------------------------------------------------------------------------------------------ small k (k <= 13)
+ * With k <= 13 the reference takes its "small k optimization" whenever it fits in memory (CKMC::AdjustMemoryLimitsSmallK, kmc.h:677-750; always when
+ * k < signature_len): no signatures, no bins. CSplitter::ProcessReadsSmallK (splitter.cpp:682-805) rolls the k-mer and its reverse complement over every buffer
+ * GetSeq returns (after HomopolymerCompressSeq with -hc) and does ++buf[kmer], ++total_kmers, kmer = min(forward, reverse complement) as 2k-bit integers with
+ * both_strands, the forward k-mer without. Its omit_next_n_kmers bookkeeping: an invalid symbol at i < k - 1 sets it to i + 1 and the counting loop, which
+ * starts at symbol k - 1, then skips the windows that end at k - 1 .. k - 1 + i — those that start at 0 .. i, all that hold symbol i; an invalid symbol at
+ * i >= k - 1 sets it to k and skips the windows that end at i .. i + k - 1, again all that hold it; a later invalid symbol only ever raises the count that
+ * is left. So: a window is counted iff it holds no invalid code, a return shorter than k adds nothing, and k = 1 is legal. The pieces of over-long lines, of
+ * long-read parts and of multi-line sequences overlap by k - 1 symbols: every window of a line lies in exactly one piece, and the windows of the returns are
+ * the windows of the RAW code stream with S1_PIECE_MARK ignored (as for k_s1_nthash_estimate) or, with -hc, of the stream k_s1_hc_compact leaves.
+ *
+ * k_s1_smallk_count<LDS_K>: direct-address counting into 4^k 64-bit counters in HBM (8 bytes at k = 1, 512 MB at k = 13). Workgroups are persistent: a
+ * workgroup takes the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of S1_TXT_TILE start positions; tile and k - 1 <= 12 halo codes in LDS (16 bytes per
+ * thread, the halo by thread 0), a strip of 16 consecutive start positions per thread, the forward and the reverse-complement k-mer rolled in one 32-bit
+ * register each (26 bits at most), the number of valid codes since the strip's start (k at most) decides validity. Equal k-mers that follow each other in a
+ * strip are merged before they are added: a homopolymer is one add of 16 per strip, not 16 adds to one address.
+ *   LDS_K > 0 (k <= LDS_K): a workgroup-private table of 4^LDS_K 32-bit counters in LDS, filled with LDS atomics and flushed ONCE per workgroup, non-zero
+ *     entries only, by relaxed agent-scope 64-bit adds. A workgroup walks at most S1_SMALLK_MAX_TILES_PER_WG tiles (2^31 windows: no counter wraps).
+ *   LDS_K = 0: 64-bit adds without return straight into the table. The lanes of a wave walk neighbouring strips and inside a homopolymer or a tandem repeat whose
+ *     period divides 16 they all hold one k-mer: the lanes that hold the k-mer of the first adding lane are added once, by that lane (one round of the
+ *     per-distinct-index aggregation of s1_nt_count, whose full loop would cost random text 64 rounds per step); the others add for themselves.
+ * *total += the windows counted: one add per workgroup. No look-back, no spin loop. */
+constexpr u32 S1_SMALLK_MAX_K = 13, S1_SMALLK_LDS_K = 7, S1_SMALLK_WGS = 1024;
+constexpr u64 S1_SMALLK_MAX_TILES_PER_WG = 1ull << 19;
+static_assert(S1_SMALLK_MAX_K - 1 <= 16 && S1_TXT_PER == 16, "the halo is one 16-byte load; a strip is a thread's 16 positions");
+
+/* called by whole waves only */
+__device__ __forceinline__ void s1_smallk_add(u64 *__restrict__ table, u32 idx, u32 cnt, bool emit)
+{
+	const u64 todo = __ballot(emit);
+	if (!todo) /* wave-uniform */
+		return;
+	const u32 lane = threadIdx.x & 63u, leader = (u32)__ffsll((unsigned long long)todo) - 1u;
+	const u32 at = __shfl(idx, (int)leader);
+	const bool mine = emit && idx == at;
+	const u64 same = __ballot(mine);
+	if (__popcll((unsigned long long)same) > 1) { /* wave-uniform */
+		const u32 sum = __shfl(wave_sum<u32>(mine ? cnt : 0u), 0);
+		if (lane == leader)
+			__hip_atomic_fetch_add(table + at, (u64)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		emit = emit && !mine;
+	}
+	if (emit)
+		__hip_atomic_fetch_add(table + idx, (u64)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int LDS_K>
+__global__ void __launch_bounds__(S1_BLOCK) k_s1_smallk_count(const int8_t *__restrict__ codes, u64 n, u32 k, u32 both_strands, u64 *__restrict__ table, u64 *total)
+{
+	static_assert(LDS_K >= 0 && LDS_K <= 7, "4^LDS_K 32-bit counters beside the tile");
+	constexpr u32 TAB = LDS_K ? 1u << (2 * LDS_K) : 1u;
+	__shared__ __attribute__((aligned(16))) int8_t s_c[S1_TXT_TILE + 16];
+	__shared__ u32 s_tab[TAB];
+	__shared__ u64 s_sum[S1_BLOCK / 64];
+	const u32 tid = threadIdx.x;
+	const u64 num_tiles = (n + S1_TXT_TILE - 1) / S1_TXT_TILE;
+	const u32 entries = 1u << (2 * k), mask = entries - 1u, rev_shift = 2 * (k - 1); /* k <= 13 (and <= LDS_K where there is one): the launcher's promise */
+	if (LDS_K)
+		for (u32 i = tid; i < entries && i < TAB; i += S1_BLOCK)
+			s_tab[i] = 0;
+	u32 counted = 0;
+	for (u64 tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) { /* the same trips for every thread of the workgroup */
+		const u64 tile0 = tile * S1_TXT_TILE;
+		__syncthreads(); /* the strips of the tile before are walked (first trip: the table is zero) */
+#pragma unroll
+		for (u32 part = 0; part < 2; ++part) {
+			if (part && tid)
+				break;
+			const u32 off = part * S1_TXT_TILE + tid * 16;
+			const u64 p0 = tile0 + off;
+			uint4 v;
+			if (p0 + 16 <= n)
+				__builtin_memcpy(&v, codes + p0, 16);
+			else {
+				int8_t b[16];
+#pragma unroll
+				for (int j = 0; j < 16; ++j)
+					b[j] = p0 + j < n ? codes[p0 + j] : (int8_t)-1;
+				__builtin_memcpy(&v, b, 16);
+			}
+			__builtin_memcpy(__builtin_assume_aligned(s_c + off, 16), &v, 16);
+		}
+		__syncthreads();
+		const u32 q0 = tid * 16, q1 = q0 + 16 + k - 1; /* q1 <= S1_TXT_TILE + 12 */
+		u32 f = 0, r = 0, len = 0, pidx = 0, pcnt = 0; /* pcnt copies of k-mer pidx wait to be added */
+		for (u32 q = q0; q < q1; ++q) {
+			const int8_t cin = s_c[q];
+			const u32 c = (u32)cin & 3u; /* S1_PIECE_MARK masked off; what an invalid code leaves in f and r is pushed out by the k valid codes a window needs */
+			f = ((f << 2) | c) & mask;
+			r = (r >> 2) | ((3u - c) << rev_shift);
+			len = cin >= 0 ? (len < k ? len + 1u : k) : 0u;
+			const bool hit = len == k; /* k valid codes since q0: the window starts at q - k + 1, inside the strip */
+			const u32 idx = both_strands && r < f ? r : f;
+			const bool emit = hit && pcnt && idx != pidx;
+			if (LDS_K) {
+				if (emit)
+					atomicAdd(&s_tab[pidx], pcnt);
+			} else
+				s1_smallk_add(table, pidx, pcnt, emit); /* every lane of the wave is here: the strips are equally long */
+			if (hit) {
+				pcnt = pcnt && idx == pidx ? pcnt + 1u : 1u;
+				pidx = idx;
+				++counted;
+			}
+		}
+		if (LDS_K) {
+			if (pcnt)
+				atomicAdd(&s_tab[pidx], pcnt);
+		} else
+			s1_smallk_add(table, pidx, pcnt, pcnt != 0);
+	}
+	if (LDS_K) {
+		__syncthreads();
+		for (u32 i = tid; i < entries && i < TAB; i += S1_BLOCK) {
+			const u32 v = s_tab[i];
+			if (v)
+				__hip_atomic_fetch_add(table + i, (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+	}
+	const u64 wsum = wave_sum<u64>((u64)counted);
+	if ((tid & 63u) == 0)
+		s_sum[tid >> 6] = wsum;
+	__syncthreads();
+	if (tid == 0) {
+		u64 all = 0;
+#pragma unroll
+		for (u32 w = 0; w < (u32)S1_BLOCK / 64; ++w)
+			all += s_sum[w];
+		if (all)
+			__hip_atomic_fetch_add(total, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+
 /* n_plus_x_recs per bin: how many (k+x)-mer records the reference's stage 2 expands each super-k-mer into (kb_collector.cpp:83-100,
  * kb_collector.h:72-118) — the third sum a CKmerBinCollector keeps, which stage 2 sizes its arrays with. One thread per super-k-mer walks
  * its k-mers comparing the first four symbols of the k-mer with those of its reverse complement. */

@@ -29,6 +29,13 @@ struct SplitApi {
 	int (*est_close)(kmc_hip_ctx *, int) = nullptr;
 	std::mutex est_mtx;
 	std::vector<char> est_on; /* per device: an estimator was opened and not drained yet */
+	/* optional, added with KMC_HIP_SPLIT_COVERS_SMALLK: a library without them (or whose kmc_hip_split_covers does not know the capability) counts no small k */
+	int (*sk_open)(kmc_hip_ctx *, int, uint32_t, uint32_t) = nullptr;
+	int (*sk_part)(kmc_hip_ctx *, int, int, const kmc_hip_split_params *, const uint8_t *, uint64_t, uint64_t *, uint64_t *) = nullptr;
+	int (*sk_read)(kmc_hip_ctx *, int, uint64_t, uint64_t, uint64_t *) = nullptr;
+	int (*sk_close)(kmc_hip_ctx *, int) = nullptr;
+	std::mutex sk_mtx;
+	std::vector<char> sk_on; /* per device: a small-k table was opened and not drained yet */
 	kmc_hip_ctx *ctx = nullptr;
 	int n_dev = 1, n_slots = 1;
 	std::string err;
@@ -49,12 +56,17 @@ void bind()
 	g_split.est_open = reinterpret_cast<decltype(g_split.est_open)>(dlsym(so, "kmc_hip_estimate_open"));
 	g_split.est_read = reinterpret_cast<decltype(g_split.est_read)>(dlsym(so, "kmc_hip_estimate_read"));
 	g_split.est_close = reinterpret_cast<decltype(g_split.est_close)>(dlsym(so, "kmc_hip_estimate_close"));
+	g_split.sk_open = reinterpret_cast<decltype(g_split.sk_open)>(dlsym(so, "kmc_hip_smallk_open"));
+	g_split.sk_part = reinterpret_cast<decltype(g_split.sk_part)>(dlsym(so, "kmc_hip_smallk_part"));
+	g_split.sk_read = reinterpret_cast<decltype(g_split.sk_read)>(dlsym(so, "kmc_hip_smallk_read"));
+	g_split.sk_close = reinterpret_cast<decltype(g_split.sk_close)>(dlsym(so, "kmc_hip_smallk_close"));
 	if (!g_split.set_map || !g_split.split_part || !g_split.last_error) {
 		g_split.err = "libkmc_hip.so lacks kmc_hip_split_set_map / kmc_hip_split_part";
 		g_split.ctx = nullptr;
 	}
 	g_split.map_hash.assign((size_t)g_split.n_dev, 0);
 	g_split.est_on.assign((size_t)g_split.n_dev, 0);
+	g_split.sk_on.assign((size_t)g_split.n_dev, 0);
 }
 
 struct HipSplitEngine : KmcSplitEngine {
@@ -64,13 +76,14 @@ struct HipSplitEngine : KmcSplitEngine {
 	std::vector<uint8_t> recs;
 	std::vector<uint64_t> arrays; /* bin_off | bin_bytes | bin_kmers | bin_superkmers | bin_plus_x */
 	std::vector<uint32_t> drain_buf; /* estimate_drain: one chunk of one device's counters */
+	std::vector<uint64_t> sk_drain_buf; /* smallk_drain: one chunk of one device's table */
 
 	uint64_t map_hash = 0; /* of this run's map: a second KMC run in the same process (library API) with another map must not split with the first one's */
 	HipSplitEngine(const KmcSplitParams &p, int dev, int slot) : P(p), dev(dev), slot(slot)
 	{
 		arrays.assign((size_t)5 * p.n_bins, 0);
 		uint64_t h = 1469598103934665603ull ^ p.signature_len; /* FNV-1a over the map's entries, once per engine */
-		const size_t n = ((size_t)1 << (2 * p.signature_len)) + 1;
+		const size_t n = p.sig_to_bin ? ((size_t)1 << (2 * p.signature_len)) + 1 : 0; /* no map: an engine of the small-k worker, which splits nothing */
 		for (size_t i = 0; i < n; ++i)
 			h = (h ^ (uint32_t)p.sig_to_bin[i]) * 1099511628211ull;
 		map_hash = h ? h : 1;
@@ -126,6 +139,75 @@ struct HipSplitEngine : KmcSplitEngine {
 		}
 		if (first + count == entries)
 			std::vector<uint32_t>().swap(drain_buf);
+		return 0;
+	}
+	bool covers_small_k() const override
+	{
+		return g_split.ctx && g_split.covers && g_split.sk_open && g_split.sk_part && g_split.sk_read && g_split.sk_close && g_split.covers(KMC_HIP_SPLIT_COVERS_SMALLK) == 1;
+	}
+	int smallk_open() override
+	{
+		if (!covers_small_k()) {
+			err = "HIP split engine: the library does not count small k on the device";
+			return KMC_HIP_EINVAL;
+		}
+		std::lock_guard<std::mutex> lck(g_split.sk_mtx);
+		if (int rc = g_split.sk_open(g_split.ctx, dev, P.kmer_len, P.both_strands ? 1u : 0u)) { /* a second engine on the device: the same pair, a no-op */
+			err = g_split.last_error(g_split.ctx);
+			return rc;
+		}
+		g_split.sk_on[dev] = 1;
+		return 0;
+	}
+	int smallk_part(const uint8_t *text, uint64_t size, bool long_read, uint64_t &n_reads, uint64_t &n_kmers) override
+	{
+		if (!covers_small_k()) {
+			err = "HIP split engine: the library does not count small k on the device";
+			return KMC_HIP_EINVAL;
+		}
+		kmc_hip_split_params hp;
+		hp.kmer_len = P.kmer_len;
+		hp.signature_len = hp.n_bins = hp.max_x = 0; /* not read */
+		hp.both_strands = P.both_strands ? 1u : 0u;
+		hp.file_type = (uint32_t)P.file_type;
+		hp.line_cap = P.line_cap;
+		hp.part_kind = long_read ? 1u : 0u;
+		hp.flags = P.homopolymer_compressed ? KMC_HIP_SPLIT_HOMOPOLYMER : 0u;
+		const int rc = g_split.sk_part(g_split.ctx, dev, slot, &hp, text, size, &n_reads, &n_kmers);
+		if (rc == KMC_HIP_UNCOVERED)
+			return KMC_SPLIT_UNCOVERED;
+		if (rc)
+			err = g_split.last_error(g_split.ctx);
+		return rc;
+	}
+	int smallk_drain(uint64_t first, uint64_t count, uint64_t *dst) override
+	{
+		const uint64_t entries = (uint64_t)1 << (2 * P.kmer_len);
+		if (!g_split.ctx || P.kmer_len > 13 || count > ((uint64_t)1 << 22) || first > entries || count > entries - first) {
+			err = "HIP split engine: smallk_drain outside the table, or more than 2^22 entries at once";
+			return KMC_HIP_EINVAL;
+		}
+		std::lock_guard<std::mutex> lck(g_split.sk_mtx);
+		sk_drain_buf.resize(count);
+		for (int d = 0; d < g_split.n_dev; ++d) {
+			if (!g_split.sk_on[d])
+				continue;
+			if (int rc = g_split.sk_read(g_split.ctx, d, first, count, sk_drain_buf.data())) {
+				err = g_split.last_error(g_split.ctx);
+				return rc;
+			}
+			for (uint64_t i = 0; i < count; ++i)
+				dst[i] += sk_drain_buf[i];
+			if (first + count == entries) {
+				g_split.sk_on[d] = 0;
+				if (int rc = g_split.sk_close(g_split.ctx, d)) {
+					err = g_split.last_error(g_split.ctx);
+					return rc;
+				}
+			}
+		}
+		if (first + count == entries)
+			std::vector<uint64_t>().swap(sk_drain_buf);
 		return 0;
 	}
 	int split_part(const uint8_t *text, uint64_t size, bool long_read, KmcSplitResult &out) override

@@ -6,7 +6,8 @@
  * GetTotal() and destructor, so CKMC<SIZE>::ProcessStage1_impl (kmc.h:1274-1362) builds against it unchanged. Compiled in with
  * `-include kb_splitter_plugin.h` ahead of kmc_runner.cpp; the reference's own splitter.cpp is compiled with -DCWSplitter=CWSplitter_ref
  * (oracle/Makefile), which is what this header declares first: CSplitter stays the reference's for what is NOT this worker (stage 0's signature
- * statistics, the small-k path and histogram estimation use it directly, kmc.h:1100-1200); this worker itself never calls it (see FAILS CLOSED below).
+ * statistics and the estimate-only worker use it directly, kmc.h:1100-1200; the small-k worker is CWSmallKSplitter_dev at the end of this header); this worker itself never calls it
+ * (see FAILS CLOSED below).
  *
  * Protocol kept from CWSplitter::operator() + CSplitter::ProcessReads + CKmerBinCollector:
  *   pq->pop(part, size, read_type) -> [engine: text -> sequences -> super-k-mers -> bin records] -> pmm_fastq->free(part)
@@ -29,8 +30,8 @@
  *             read of mem_part_pmm_reads bases or more.
  * Parts the reader labelled ReadType::long_read (queues.h:40) and lines of mem_part_pmm_reads symbols or more go through the engine like any other, and so
  * do the ReadType::na parts of multi-line FASTA (fastq_reader.cpp:399-468, :579-583) with an engine that covers them (file_type 2). With -hc the engine
- * compresses every return of GetSeq on its own, as ProcessReads does (splitter.cpp:575-581); stage 0, the small-k worker and the estimate worker stay the
- * reference's and honour the flag themselves, and n_reads does not depend on it.
+ * compresses every return of GetSeq on its own, as ProcessReads does (splitter.cpp:575-581); stage 0 and the estimate worker stay the
+ * reference's and honour the flag themselves (the small-k worker below passes it to its engine), and n_reads does not depend on it.
  * With --opt-out-size (ESTIMATE_AND_COUNT_KMERS) the reference's splitter hashes every k-mer a second time into Queues.ntHashEstimator (splitter.cpp:576-577),
  * an object that exists before the workers are constructed (kmc.h:1277-1293). Here the engine keeps those counters where it splits: every worker opens the
  * estimator of its engine's device with the object's own s and r, the LAST worker to finish adds the counters of every device into the object's arrays
@@ -122,6 +123,24 @@ inline uint32_t s_of(CntHashEstimator &e) { return e.*Stowed<S>::value; }
 inline uint32_t r_of(CntHashEstimator &e) { return e.*Stowed<R>::value; }
 inline uint32_t *counters_of(CntHashEstimator &e, int type) { return (e.*Stowed<Counters>::value)[type]; }
 } // namespace kmc_hip_est_access
+
+/* KMC_SPLIT_UNCOVERED: what stops the run, by the kind of part (both workers of this header) */
+static inline void kmc_hip_s1_stop_uncovered_part(InputType file_type, ReadType read_type)
+{
+	if (file_type == InputType::BAM)
+		CCriticalErrorHandler::Inst().HandleCriticalError(
+		    "Error: stage 1 on the device: a part of the BAM input is not covered: its alignment records do not end exactly at the end of the part, a "
+		    "block_size is smaller than its record's header, name, cigar, bases and qualities (or negative), or a read that is counted has "
+		    "mem_part_pmm_reads bases or more. Run this input with kmc_hip (the reference's stage 1, stage 2 on the device).");
+	if (read_type == ReadType::na)
+		CCriticalErrorHandler::Inst().HandleCriticalError(
+		    "Error: stage 1 on the device: a part of the multi-line FASTA input ends inside a title line (a title longer than the reader's part). "
+		    "Run this input with kmc_hip (the reference's stage 1, stage 2 on the device).");
+	CCriticalErrorHandler::Inst().HandleCriticalError(
+	    "Error: stage 1 on the device: a part of the input is malformed FASTA / FASTQ text (a blank line, a quality string of another length than its "
+	    "sequence, a control character or a lone carriage return). The device splitter does not guess what such text means; "
+	    "run this input with kmc_hip (the reference's stage 1, stage 2 on the device).");
+}
 
 class CWSplitter {
 	struct BinBuf {
@@ -379,19 +398,7 @@ public:
 					continue;
 				}
 #endif
-				if (params->file_type == InputType::BAM)
-					CCriticalErrorHandler::Inst().HandleCriticalError(
-					    "Error: stage 1 on the device: a part of the BAM input is not covered: its alignment records do not end exactly at the end of the part, a "
-					    "block_size is smaller than its record's header, name, cigar, bases and qualities (or negative), or a read that is counted has "
-					    "mem_part_pmm_reads bases or more. Run this input with kmc_hip (the reference's stage 1, stage 2 on the device).");
-				if (read_type == ReadType::na)
-					CCriticalErrorHandler::Inst().HandleCriticalError(
-					    "Error: stage 1 on the device: a part of the multi-line FASTA input ends inside a title line (a title longer than the reader's part). "
-					    "Run this input with kmc_hip (the reference's stage 1, stage 2 on the device).");
-				CCriticalErrorHandler::Inst().HandleCriticalError(
-				    "Error: stage 1 on the device: a part of the input is malformed FASTA / FASTQ text (a blank line, a quality string of another length than its "
-				    "sequence, a control character or a lone carriage return). The device splitter does not guess what such text means; "
-				    "run this input with kmc_hip (the reference's stage 1, stage 2 on the device).");
+				kmc_hip_s1_stop_uncovered_part(params->file_type, read_type);
 			}
 			if (rc != 0) {
 				std::ostringstream ostr;
@@ -432,5 +439,149 @@ public:
 	}
 	~CWSplitter() {}
 };
+
+/* ---- the small-k worker (k <= 13, "Small k optimization on!": kmc.h:677-750, :767-862) ----
+ * Drop-in for the reference's CWSmallKSplitter<uint64_t> (splitter.h:138-171, splitter.cpp:929-983): constructor (Params, Queues), operator()(), GetTotal,
+ * GetResult, GetTotalKmers, Release, so that kmc.h:84, :799 and the reference's own small-k stage 2 (ProcessSmallKOptimization_Stage2 kmc.h:865-960,
+ * CSmallKCompleter) build against it unchanged. The reference's class keeps its name and stays linkable (splitter.cpp instantiates it); this one has a name
+ * of its own, and the #define at the end of this header points kmc.h at it.
+ * With an engine that covers_small_k() the parts are counted where the engine counts them, into ONE table per device: the worker reserves and zeroes its own
+ * table from pmm_small_k_buf exactly as the reference's does (stage 2 sums the tables of all n_splitters workers, kmc.h:872-885), pops parts, calls
+ * smallk_part, frees each part and sums n_reads and n_kmers; the LAST worker to finish adds every device's table into its own, in chunks of 32 MB, and the
+ * others hand over zeros. A part the engine answers KMC_SPLIT_UNCOVERED or an error for stops the run like a part of the bin worker does.
+ * With any other engine (the oracle and emulated engines, a library without kmc_hip_smallk_*) — or one that lacks the job's format or -hc — the whole job
+ * goes to the reference's CWSmallKSplitter, as it did before this worker existed. --opt-out-size and -e never get here (kmc.h:773-779). */
+template <typename COUNTER_TYPE> using CWSmallKSplitter_ref = CWSmallKSplitter<COUNTER_TYPE>;
+
+template <typename COUNTER_TYPE> class CWSmallKSplitter_dev {
+	static_assert(sizeof(COUNTER_TYPE) == sizeof(uint64_t), "the engine's table has 64-bit counters (kmc.h:84 uses uint64_t)");
+	CPartQueue *pq;
+	CMemoryPool *pmm_fastq, *pmm_small_k;
+	CKMCParams *params;
+	CSmallKBuf<COUNTER_TYPE> small_k_buf;
+	std::unique_ptr<CWSmallKSplitter_ref<COUNTER_TYPE>> ref; /* non-null: the reference's worker runs the whole job */
+	std::unique_ptr<KmcSplitEngine> engine;
+	uint64 n_reads = 0, total_kmers = 0;
+	uint32 kmer_len;
+	uint64 st_parts = 0;
+	long long st_engine_ns = 0;
+
+	static std::atomic<int> &finished_workers()
+	{
+		static std::atomic<int> finished{0};
+		return finished;
+	}
+	void drain()
+	{
+		const uint64_t entries = (uint64_t)1 << (2 * kmer_len), chunk = (uint64_t)1 << 22; /* 32 MB of counters at a time */
+		KmcTimeline::mark("splitter: small k, drain of the device tables starts");
+		for (uint64_t at = 0; at < entries; at += chunk)
+			if (int rc = engine->smallk_drain(at, entries - at < chunk ? entries - at : chunk, reinterpret_cast<uint64_t *>(small_k_buf.buf) + at)) {
+				std::ostringstream ostr;
+				ostr << "Error: stage-1 split engine failed to hand over the small-k table (code " << rc << "): " << engine->last_error();
+				CCriticalErrorHandler::Inst().HandleCriticalError(ostr.str());
+			}
+		KmcTimeline::mark("splitter: small k, device tables merged");
+	}
+
+public:
+	CWSmallKSplitter_dev(CKMCParams &Params, CKMCQueues &Queues)
+	{
+		pq = Queues.part_queue.get();
+		pmm_fastq = Queues.pmm_fastq.get();
+		pmm_small_k = Queues.pmm_small_k_buf.get();
+		params = &Params;
+		kmer_len = Params.kmer_len;
+		small_k_buf.buf = nullptr;
+		KmcSplitParams sp;
+		sp.kmer_len = Params.kmer_len;
+		sp.signature_len = Params.signature_len; /* may exceed kmer_len: not used on this path */
+		sp.n_bins = Params.n_bins;
+		sp.max_x = 0;
+		sp.both_strands = Params.both_strands ? 1 : 0;
+		sp.file_type = Params.file_type == InputType::FASTQ ? 1 : Params.file_type == InputType::MULTILINE_FASTA ? 2 : Params.file_type == InputType::BAM ? 4 : 0; /* KMC: 0 */
+		sp.line_cap = (uint64_t)Params.mem_part_pmm_reads; /* (MAX_LINE_SIZE + 1) * 8 in this mode, kmc.h:689 */
+		sp.sig_to_bin = nullptr;                           /* no signature mapper exists in this mode */
+		sp.homopolymer_compressed = Params.homopolymer_compressed ? 1 : 0;
+		static std::atomic<int> next_idx{0};
+		engine.reset(kmc_make_split_engine(sp, next_idx++ % (int)Params.n_splitters, (int)Params.n_splitters));
+		const bool covered = engine && engine->covers_small_k() && (Params.file_type != InputType::MULTILINE_FASTA || engine->covers_multiline_fasta()) &&
+		                     (Params.file_type != InputType::BAM || engine->covers_bam()) && (!Params.homopolymer_compressed || engine->covers_homopolymer_compression());
+		if (!covered) {
+			engine.reset();
+			ref = std::make_unique<CWSmallKSplitter_ref<COUNTER_TYPE>>(Params, Queues);
+			return;
+		}
+		finished_workers() = 0; /* every worker is constructed before any can finish (kmc.h:797-801), as in CWSplitter above */
+		if (int rc = engine->smallk_open()) {
+			std::ostringstream ostr;
+			ostr << "Error: stage-1 split engine could not open the small-k table (code " << rc << "): " << engine->last_error();
+			CCriticalErrorHandler::Inst().HandleCriticalError(ostr.str());
+		}
+	}
+	~CWSmallKSplitter_dev() {}
+
+	void operator()()
+	{
+		if (ref) {
+			(*ref)();
+			return;
+		}
+		KmcTimeline::mark_first_last("splitter: first worker started", nullptr);
+		pmm_small_k->reserve(small_k_buf.buf); /* splitter.cpp:954-955 */
+		memset(small_k_buf.buf, 0, ((size_t)1 << (2 * kmer_len)) * sizeof(*small_k_buf.buf));
+		while (!pq->completed()) {
+			uchar *part;
+			uint64 size;
+			ReadType read_type;
+			if (!pq->pop(part, size, read_type))
+				continue;
+			if (read_type == ReadType::na && params->file_type != InputType::MULTILINE_FASTA && params->file_type != InputType::BAM)
+				CCriticalErrorHandler::Inst().HandleCriticalError("Error: stage 1 on the device got a part of ReadType::na");
+			uint64_t part_reads = 0, part_kmers = 0;
+			const auto t0 = std::chrono::steady_clock::now();
+			const int rc = engine->smallk_part(part, size, read_type == ReadType::long_read, part_reads, part_kmers);
+			st_engine_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+			if (rc == KMC_SPLIT_UNCOVERED)
+				kmc_hip_s1_stop_uncovered_part(params->file_type, read_type);
+			if (rc != 0) {
+				std::ostringstream ostr;
+				ostr << "Error: stage-1 split engine failed (code " << rc << "): " << engine->last_error();
+				CCriticalErrorHandler::Inst().HandleCriticalError(ostr.str());
+			}
+			++st_parts;
+			pmm_fastq->free(part);
+			n_reads += part_reads;
+			total_kmers += part_kmers;
+		}
+		if (++finished_workers() == (int)params->n_splitters)
+			drain();
+		engine.reset();
+		KmcTimeline::mark_first_last(nullptr, "splitter: last worker done");
+		if (getenv("KMC_HIP_VERBOSE"))
+			fprintf(stderr, "[kmc_hip stage 1] worker: small k on the device: %llu parts, %llu k-mers (%.3f s inside the engine)%s\n", (unsigned long long)st_parts,
+			        (unsigned long long)total_kmers, st_engine_ns * 1e-9, params->homopolymer_compressed ? ", homopolymer-compressed (-hc) on the device" : "");
+	}
+
+	void GetTotal(uint64 &_n_reads)
+	{
+		if (ref) {
+			ref->GetTotal(_n_reads);
+			return;
+		}
+		_n_reads = n_reads;
+	}
+	CSmallKBuf<COUNTER_TYPE> GetResult() { return ref ? ref->GetResult() : small_k_buf; }
+	uint64 GetTotalKmers() { return ref ? ref->GetTotalKmers() : total_kmers; }
+	void Release()
+	{
+		if (ref)
+			ref->Release();
+		else
+			pmm_small_k->free(small_k_buf.buf);
+	}
+};
+/* from here on (kmc.h is read after this header) the small-k worker of CKMC<SIZE> is the one above */
+#define CWSmallKSplitter CWSmallKSplitter_dev
 
 #endif

@@ -63,6 +63,19 @@ struct KmcSplitEngine {
 	virtual bool covers_histogram_estimation() const { return false; }
 	virtual int estimate_open() { return -1; }
 	virtual int estimate_drain(uint64_t /*first*/, uint64_t /*count*/, uint32_t * /*dst*/) { return -1; }
+	/* small k (k <= 13, the reference's "small k optimization": CWSmallKSplitter, splitter.cpp:929-983, over CSplitter::ProcessReadsSmallK :682-805): the engine keeps
+	 * ONE table of 4^kmer_len 64-bit counters wherever its parts are counted, instead of one per worker. An engine made for this path gets sig_to_bin = nullptr
+	 * (there is no signature map in this mode) and must not need signature_len, n_bins or max_x; only kmer_len, both_strands, file_type, line_cap and
+	 * homopolymer_compressed count.
+	 * smallk_open : makes the (zeroed) table of this engine's device; once per engine, in front of its first part. 0 or an error code.
+	 * smallk_part : counts one part: n_reads as split_part gives it, n_kmers = the k-mers counted (CSplitter::total_kmers). 0, a negative error code or
+	 *               KMC_SPLIT_UNCOVERED; a call that does not return 0 has added nothing.
+	 * smallk_drain: when every engine of the run has counted its last part: ADDS entries [first, first + count) of the table of every device one was opened on
+	 *               to dst[0 .. count), count <= 2^22 (32 MB); the call that takes the last entry also closes the tables. 0 or an error code. */
+	virtual bool covers_small_k() const { return false; }
+	virtual int smallk_open() { return -1; }
+	virtual int smallk_part(const uint8_t * /*text*/, uint64_t /*size*/, bool /*long_read*/, uint64_t & /*n_reads*/, uint64_t & /*n_kmers*/) { return -1; }
+	virtual int smallk_drain(uint64_t /*first*/, uint64_t /*count*/, uint64_t * /*dst*/) { return -1; }
 };
 
 /* Provided by exactly one engine implementation linked into the binary. */
