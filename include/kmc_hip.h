@@ -202,6 +202,50 @@ int kmc_hip_process_bins_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_par
 int kmc_hip_order_database_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_params *params, const kmc_hip_bin_desc *bins, uint64_t n_bins,
                                   uint32_t out_lut_prefix_len, uint8_t *d_out, uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers);
 
+/* ---- set operations between two ordered databases --------------------------------------------------
+ * `kmc_tools simple <db1> <db2> <operation> <out>` on the device. Each input is a database BODY as kmc_hip_order_database_device leaves it and kmc_tools writes
+ * it (KMC1): n_recs ascending records of (kmer_len - lut_prefix_len) / 4 suffix bytes (most significant first) + counter_size counter bytes (least significant
+ * first), and a LUT of 4^lut_prefix_len uint64 where entry i is the number of records with a prefix below i. The inputs share kmer_len (<= 224) and may differ in
+ * lut_prefix_len and counter_size. A record whose count lies outside its input's [cutoff_min, cutoff_max] is treated as absent, as the reference's readers do
+ * (kmc_tools/kmc1_db_reader.h:574-576,618). The two sequences are merged; every k-mer is only in A, only in B, or in both, and
+ *   INTERSECT keeps the pairs, UNION everything, KMERS_SUBTRACT what is only in A, COUNTERS_SUBTRACT what is only in A and the pairs, and the REVERSE_ operations
+ *   the same with the inputs' roles swapped (operations.h:317-322);
+ *   a pair's count is counter_op(count in A, count in B) in 32-bit unsigned arithmetic — SUM wraps, DIFF is 0 when the left count is not larger — with the counts
+ *   swapped for REVERSE_COUNTERS_SUBTRACT (operations.h:337-340, bundle.h:257-278); the two KMERS_SUBTRACT operations ignore counter_op;
+ *   then the writer's rule (kmc1_db_writer.h:382-385): a count below the output's cutoff_min (>= 1) or above its cutoff_max is dropped, what is left is clamped to
+ *   counter_max (>= 1).
+ * d_out receives the kept records in ascending order, packed for out_lut_prefix_len and a counter of MIN(BYTE_LOG(counter_max), BYTE_LOG(cutoff_max)) bytes
+ * (kmc1_db_writer.h:154; that is kmc_hip_counter_size(cutoff_max, counter_max), except that counter_max == 1 still stores one byte here), d_lut_out the LUT of
+ * 4^out_lut_prefix_len entries. out_capacity (bytes) must hold the operation's upper bound: the records of both inputs for UNION, of the smaller input for
+ * INTERSECT, of A for the two SUBTRACT operations, of B for the two REVERSE_ ones — KMC_HIP_ECAPACITY otherwise. KMC_HIP_EINVAL: a NULL argument, a counter_size
+ * outside 1..4, a lut_prefix_len with (kmer_len - lut_prefix_len) % 4 != 0; KMC_HIP_ECORRUPT: a LUT whose last entry exceeds n_recs. Either input may be empty
+ * (d_recs may then be NULL). Synchronous. *n_kmers = records written = stats[KMC_HIP_DB_STAT_WRITTEN]; the header and the markers around the body are the caller's
+ * (kmc_amd/dbio.py writes them).
+ * Replaces: CSimpleOperation<SIZE>::process_impl (kmc_tools/operations.h:298-491), a single-threaded two-pointer merge, feeding CKMC1DbWriter<SIZE>::add_kmer
+ * (kmc1_db_writer.h:375-404). */
+enum { KMC_HIP_DB_INTERSECT = 0, KMC_HIP_DB_UNION = 1, KMC_HIP_DB_KMERS_SUBTRACT = 2, KMC_HIP_DB_COUNTERS_SUBTRACT = 3, KMC_HIP_DB_REVERSE_KMERS_SUBTRACT = 4,
+       KMC_HIP_DB_REVERSE_COUNTERS_SUBTRACT = 5 };
+enum { KMC_HIP_DB_CNT_MIN = 0, KMC_HIP_DB_CNT_MAX = 1, KMC_HIP_DB_CNT_SUM = 2, KMC_HIP_DB_CNT_DIFF = 3, KMC_HIP_DB_CNT_LEFT = 4, KMC_HIP_DB_CNT_RIGHT = 5 };
+/* stats[]: k-mers in both inputs / only in A / only in B (after the inputs' cutoffs), candidates the output's cutoff_min / cutoff_max dropped, records written */
+enum { KMC_HIP_DB_STAT_PAIRS = 0, KMC_HIP_DB_STAT_ONLY_A = 1, KMC_HIP_DB_STAT_ONLY_B = 2, KMC_HIP_DB_STAT_BELOW_MIN = 3, KMC_HIP_DB_STAT_ABOVE_MAX = 4, KMC_HIP_DB_STAT_WRITTEN = 5 };
+typedef struct kmc_hip_db_view { /* one input: a KMC1 body on the device */
+	const uint8_t *d_recs;
+	uint64_t n_recs;
+	const uint64_t *d_lut;
+	uint32_t lut_prefix_len, counter_size; /* counter_size 1..4; 0 is KMC_HIP_EINVAL */
+	uint32_t cutoff_min;
+	uint64_t cutoff_max; /* the input's -ci / -cx */
+} kmc_hip_db_view;
+typedef struct kmc_hip_db_op {
+	uint32_t op;         /* KMC_HIP_DB_INTERSECT .. KMC_HIP_DB_REVERSE_COUNTERS_SUBTRACT */
+	uint32_t counter_op; /* KMC_HIP_DB_CNT_MIN .. _RIGHT (ignored by the two kmers_subtract operations) */
+	uint32_t cutoff_min, counter_max;
+	uint64_t cutoff_max; /* of the output */
+	uint32_t out_lut_prefix_len;
+} kmc_hip_db_op;
+int kmc_hip_db_set_op_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *a, const kmc_hip_db_view *b, const kmc_hip_db_op *op, uint8_t *d_out,
+                             uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers, uint64_t stats[6]);
+
 /* ---- end-of-run tallies ---------------------------------------------------------------------- */
 
 /* Sum stats[4] over the context's devices with one RCCL all-reduce (ncclUint64 x 4, ncclSum) over xGMI.

@@ -86,6 +86,26 @@ SMALLK_MAX_K = 13
 SPLIT_COVERS_HOMOPOLYMER = 0x100  # KMC_HIP_SPLIT_COVERS_HOMOPOLYMER: ask kmc_hip_split_covers before setting the flag (an older library ignores it)
 
 
+class DbView(C.Structure):
+    """struct kmc_hip_db_view: one input of kmc_hip_db_set_op_device, a KMC1 database body on the device"""
+
+    _fields_ = [("d_recs", C.c_void_p), ("n_recs", C.c_uint64), ("d_lut", C.c_void_p), ("lut_prefix_len", C.c_uint32), ("counter_size", C.c_uint32),
+                ("cutoff_min", C.c_uint32), ("cutoff_max", C.c_uint64)]
+
+
+class DbOp(C.Structure):
+    """struct kmc_hip_db_op: operation, counter mode and the output's cutoffs of kmc_hip_db_set_op_device"""
+
+    _fields_ = [("op", C.c_uint32), ("counter_op", C.c_uint32), ("cutoff_min", C.c_uint32), ("counter_max", C.c_uint32), ("cutoff_max", C.c_uint64),
+                ("out_lut_prefix_len", C.c_uint32)]
+
+
+# KMC_HIP_DB_*: the operations of `kmc_tools simple` and its -oc counter modes, by the names the command line uses
+DB_OPS = {"intersect": 0, "union": 1, "kmers_subtract": 2, "counters_subtract": 3, "reverse_kmers_subtract": 4, "reverse_counters_subtract": 5}
+DB_COUNTER_OPS = {"min": 0, "max": 1, "sum": 2, "diff": 3, "left": 4, "right": 5}
+DB_STATS = ("n_pairs", "n_only_a", "n_only_b", "n_below_min", "n_above_max", "n_written")  # stats[] of kmc_hip_db_set_op_device, in order
+
+
 def make_params(k, both_strands=1, cutoff_min=2, cutoff_max=10**9, counter_max=255, lut_prefix_len=3, output_type=0,
                 without_output=0) -> BinParams:
     return BinParams(k, both_strands, cutoff_min, without_output, cutoff_max, counter_max, lut_prefix_len, output_type)
@@ -106,6 +126,7 @@ SYMBOLS = [
     "kmc_hip_split_reads_plan", "kmc_hip_split_reads_emit", "kmc_hip_split_reads_free",
     "kmc_hip_split_set_map", "kmc_hip_split_part", "kmc_hip_split_covers", "kmc_hip_estimate_open", "kmc_hip_estimate_read", "kmc_hip_estimate_close",
     "kmc_hip_smallk_open", "kmc_hip_smallk_part", "kmc_hip_smallk_read", "kmc_hip_smallk_close",
+    "kmc_hip_db_set_op_device",
 ]
 
 _LIB = None
@@ -195,6 +216,8 @@ def load():
         L.kmc_hip_smallk_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(SplitParams), vp, C.c_uint64, u64p, u64p]
         L.kmc_hip_smallk_read.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp]
         L.kmc_hip_smallk_close.argtypes = [vp, C.c_int]
+    if hasattr(L, "kmc_hip_db_set_op_device"):  # added within ABI version 4
+        L.kmc_hip_db_set_op_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.POINTER(DbView), C.POINTER(DbOp), vp, C.c_uint64, vp, u64p, u64p]
     _LIB = L
     return L
 
@@ -426,6 +449,15 @@ class Context:
         n = C.c_uint64()
         self._chk(self.L.kmc_hip_order_database_device(self.h, dev, C.byref(p), descs, len(descs), out_lut_prefix_len, d_out, out_capacity, d_lut_out, C.byref(n)))
         return n.value
+
+    def db_set_op_device(self, kmer_len: int, a: DbView, b: DbView, op: DbOp, d_out: int, out_capacity: int, d_lut_out: int, dev: int = 0):
+        """One `kmc_tools simple` operation between two device-resident KMC1 bodies (kmc_hip_db_set_op_device); returns (records written, dict of the six tallies)."""
+        if not hasattr(self.L, "kmc_hip_db_set_op_device"):
+            raise KmcHipError(-1, f"{lib_path()} has no kmc_hip_db_set_op_device")
+        n = C.c_uint64()
+        st = (C.c_uint64 * 6)()
+        self._chk(self.L.kmc_hip_db_set_op_device(self.h, dev, kmer_len, C.byref(a), C.byref(b), C.byref(op), d_out, out_capacity, d_lut_out, C.byref(n), st))
+        return n.value, dict(zip(DB_STATS, (int(x) for x in st)))
 
     def host_alloc(self, nbytes: int) -> np.ndarray:
         """Pinned host memory as a uint8 array (free with host_free(arr))."""

@@ -59,7 +59,7 @@ int order_database_t(Slot &s, const DevParams &P, const kmc_hip_bin_desc *bins, 
 			continue;
 		k_db_cumsum<<<dim3(1), dim3(256), 0, s.stream>>>((const u64 *)bins[b].d_lut, n_entries, sums);
 		k_db_unpack<SIZE><<<dim3((u32)((n_of[b] + 255) / 256)), dim3(256), 0, s.stream>>>(bins[b].d_out, n_of[b], sums, (u32)n_entries, P.k, P.lut_prefix_len, P.sbytes, P.cbytes,
-		                                                                             recs + off * W);
+		                                                                             recs + off * W, 0u, ~0ull);
 		off += n_of[b];
 	}
 	HIPCHK(hipGetLastError());
@@ -71,7 +71,7 @@ int order_database_t(Slot &s, const DevParams &P, const kmc_hip_bin_desc *bins, 
 			return rc;
 	HIPCHK(hipMemsetAsync(d_lut_out, 0, (1ull << (2 * p_out)) * 8, s.stream));
 	if (n_total)
-		k_db_pack<SIZE><<<dim3((u32)((n_total + 255) / 256)), dim3(256), 0, s.stream>>>(sorted, n_total, P.k, p_out, P.cbytes, d_out, d_lut_out);
+		k_db_pack<SIZE><<<dim3((u32)((n_total + 255) / 256)), dim3(256), 0, s.stream>>>(sorted, n_total, P.k, p_out, P.cbytes, d_out, d_lut_out, (const u64 *)nullptr);
 	HIPCHK(hipGetLastError());
 	return 0;
 }

@@ -426,3 +426,4 @@ int read_and_clear_sticky(Slot &s, u32 &err)
 #include "host_cabi_stage2.hip.h" /* the C-ABI of stage 2: lifetime, narrow boundary, full boundary (one bin / several bins per call, device-resident batches) */
 #include "host_cabi_stage1.hip.h" /* the C-ABI test hooks and stage 1 on the device (reads -> bins in HBM; one part of input text -> bin records) */
 #include "host_cabi_collective.hip.h" /* the tally all-reduce over the devices of a context (RCCL) and the instrumentation entries */
+#include "host_setops.hip.h" /* set operations between two ordered databases (`kmc_tools simple`) */
