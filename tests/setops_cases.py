@@ -26,7 +26,12 @@ LINES = [(op, [], [], op, []) for op in OPS] + [
     ("union_ci3_cx20_cs10", [], [], "union", ["-ci3", "-cx20", "-cs10"]),
     ("union_a_ci2_b_cx5", ["-ci2"], ["-cx5"], "union", []),
 ]
-PAIRS = (27, 55)
+PAIRS = (27, 55, 33)
+# k = 33: inputs of more than 8 160 k-mers, where kmc_tools itself picks lut_prefix_len 5 — the prefix lies across a 64-bit word boundary of the k-mer
+LINES_OF = {27: LINES, 55: LINES, 33: [ln for ln in LINES if ln[0] in ("union", "intersect", "counters_subtract")]}
+GOLDEN_CASES = [(k, ln) for k in PAIRS for ln in LINES_OF[k]]
+GOLDEN_IDS = [f"{ln[0]}-{k}" for k, ln in GOLDEN_CASES]
+RAW_A = {33: "raw_a"}  # the KMC2 database `kmc` wrote for input a (records ordered inside every signature bin), kept next to what `transform sort` made of it
 
 
 def golden_path(k, name):
@@ -70,7 +75,7 @@ def encode_body(k, p, cs, kmers, counts):
     for x, c in zip(kmers, counts):
         out += (x & ((1 << (2 * (k - p))) - 1)).to_bytes(sb, "big") + (c & ((1 << (8 * cs)) - 1)).to_bytes(cs, "little")
         prefixes.append(x >> (2 * (k - p)))
-    lut = np.array([bisect.bisect_left(prefixes, i) for i in range(1 << (2 * p))], dtype=np.uint64)
+    lut = np.searchsorted(np.array(prefixes, dtype=np.uint64), np.arange(1 << (2 * p), dtype=np.uint64), side="left").astype(np.uint64)  # entry i: records with a prefix below i
     return lut, np.frombuffer(bytes(out), dtype=np.uint8).copy()
 
 
@@ -198,11 +203,34 @@ def random_kmers(rng, k, n, lo_prefix=None, p=None):
     return sorted(base | x for x in s)
 
 
-def planted_cases(k, tile, seed=5):
-    """-> list of (name, a, b, kwargs of check_case). `tile`: records of a merge tile of the library under test; the databases are 3-4 tiles long."""
+def straddles(k, p):
+    """the p-symbol prefix of a k-mer lies across a 64-bit word boundary: its lowest bit is bit 2 (k - p)"""
+    return (2 * (k - p)) % 64 + 2 * p > 64
+
+
+def default_prefix_lens(k):
+    return [p for p in (1, 2, 3, 4, 5, 6, 7) if (k - p) % 4 == 0][0], [p for p in (5, 6, 7, 4) if (k - p) % 4 == 0][0], [p for p in (3, 4, 1, 2) if (k - p) % 4 == 0][0]
+
+
+REDUCED = ("mixed_", "equal_", "first_prefix", "last_prefix", "one_prefix")  # the reduced list: the names that start like this
+
+# (k, prefix lengths of A, B and the output or None: default_prefix_lens, reduced list): what test_device_call_on_planted_databases runs. SIZE 1 (k = 27, 32, 33: the
+# prefix across the word boundary), 2 (35: likewise; 55), 3 (65, 96), 4 (127), 5 (129), 6 (161), 7 (193, 224: the widest). At every straddling k each of the three
+# prefixes straddles in some format
+PLANTED = [(27, None, False), (32, None, False), (55, None, False), (127, None, False),
+           (33, (5, 9, 5), True), (33, (1, 5, 9), True), (35, (7, 3, 7), True), (35, (3, 7, 3), True), (65, (5, 9, 5), True), (96, (4, 8, 4), True),
+           (129, (9, 5, 9), True), (161, (5, 9, 5), True), (193, (9, 5, 9), True), (224, (4, 8, 4), True)]
+PLANTED_IDS = [str(k) if pl is None else f"{k}-p{pl[0]}.{pl[1]}.{pl[2]}" for k, pl, _ in PLANTED]
+for _k in (33, 35, 65, 129, 161, 193):
+    assert all(any(straddles(_k, pl[q]) for k, pl, _ in PLANTED if k == _k) for q in range(3)), _k
+
+
+def planted_cases(k, tile, seed=5, prefix_lens=None, reduced=False):
+    """-> list of (name, a, b, kwargs of check_case). `tile`: records of a merge tile of the library under test; the databases are 3-4 tiles long.
+    prefix_lens: lut_prefix_len of A, of B and of the output (default: default_prefix_lens(k)); reduced: only the cases named in REDUCED"""
     rng = np.random.default_rng(seed + k)
     n = 3 * tile + tile // 3 + 7
-    p_a, p_b, p_o = [p for p in (1, 2, 3, 4, 5, 6, 7) if (k - p) % 4 == 0][0], [p for p in (5, 6, 7, 4) if (k - p) % 4 == 0][0], [p for p in (3, 4, 1, 2) if (k - p) % 4 == 0][0]
+    p_a, p_b, p_o = prefix_lens or default_prefix_lens(k)
     cnt = lambda m, hi=200: [int(x) for x in rng.integers(1, hi, size=m)]  # noqa: E731
     all_k = random_kmers(rng, k, 2 * n)
     same = all_k[1::2][:n]
@@ -243,6 +271,38 @@ def planted_cases(k, tile, seed=5):
     cases.append(("wrap_sum", (tk, top), (tk, [1, 2, U32, U32, U32 - 1, 5][: len(top)]), dict(f4, op="union", oc="sum")))
     cases.append(("diff_to_zero", (tk, top), (tk, [U32, U32, 1, 5, 2, U32 - 1][: len(top)]), dict(f4, op="counters_subtract", oc="diff")))
     cases.append(("reverse_diff_to_zero", (tk, top), (tk, [U32, U32, 1, 5, 2, U32 - 1][: len(top)]), dict(f4, op="reverse_counters_subtract", oc="diff")))
+    return [c for c in cases if c[0].startswith(REDUCED)] if reduced else cases
+
+
+SEAM_OPS = (("union", "sum"), ("intersect", "min"), ("counters_subtract", "diff"), ("reverse_kmers_subtract", "diff"))
+SEAMS = [(27, None), (55, None), (33, (5, 9, 5))]  # (k, prefix lengths): what test_cut_records_on_every_tile_seam runs
+SEAM_IDS = ["27", "55", "33-p5.9.5"]
+
+
+def seam_cut_cases(k, tile, prefix_lens=None, seed=11):
+    """Records cut by their INPUT'S cutoffs on every tile seam. A and B hold the same keys, so the merged sequence is A0 B0 A1 B1 ...: in one parity every seam
+    falls between two pairs, in the other (one smallest A-only record in front) inside a pair — A's record the last of a tile, its partner B's the first of the
+    next, each seen by the other through the halo. Who is cut is chosen by position: all of A, all of B, A at even and B at odd positions, and the converse —
+    so on every seam one side or the other is cut, in the slice or in the halo. A count below its input's cutoff_min (2 against 10) or above its cutoff_max
+    (240 against 99) is cut. -> list of (name, a, b, kwargs of check_case)"""
+    rng = np.random.default_rng(seed + k)
+    n = 3 * tile + tile // 3 + 7
+    p_a, p_b, p_o = prefix_lens or default_prefix_lens(k)
+    same = random_kmers(rng, k, n + 1)[1:]  # none of them 0
+    in_cut, kept = (10, 99), (1, 255)
+
+    def counts(m, is_cut):
+        c = [int(x) for x in rng.integers(10, 100, size=m)]
+        return [(2 if i & 2 else 240) if is_cut(i) else c[i] for i in range(m)]
+
+    patterns = (("all_a_cut", lambda i: True, lambda i: False), ("all_b_cut", lambda i: False, lambda i: True),
+                ("a_even_b_odd_cut", lambda i: i % 2 == 0, lambda i: i % 2 == 1), ("a_odd_b_even_cut", lambda i: i % 2 == 1, lambda i: i % 2 == 0))
+    cases = []
+    for parity, ka in (("pairs", same), ("shifted", [0] + same)):
+        for pname, cut_a, cut_b in patterns:
+            a, b = (ka, counts(len(ka), cut_a)), (same, counts(n, cut_b))
+            for op, oc in SEAM_OPS:
+                cases.append((f"{pname}_{parity}_{op}", a, b, dict(a_fmt=(p_a, 1), b_fmt=(p_b, 1), p_out=p_o, op=op, oc=oc, a_cut=in_cut, b_cut=in_cut, ci=kept[0], cx=kept[1], cs=255)))
     return cases
 
 
@@ -269,6 +329,9 @@ class LibContext:
         L.kmc_hip_db_set_op_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(capi.DbView), C.POINTER(capi.DbView), C.POINTER(capi.DbOp), vp, C.c_uint64, vp,
                                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.kmc_hip_counter_size.argtypes = [C.c_uint64, C.c_uint64]
+        L.kmc_hip_out_rec_bytes.argtypes = [C.POINTER(capi.BinParams)]
+        L.kmc_hip_out_rec_bytes.restype = C.c_uint32
+        L.kmc_hip_order_database_device.argtypes = [vp, C.c_int, C.POINTER(capi.BinParams), C.POINTER(capi.BinDesc), C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         h = vp()
         ids = (C.c_int * 1)(0)
         assert L.kmc_hip_init(ids, 1, C.byref(h)) == 0
@@ -296,6 +359,14 @@ class LibContext:
 
     def d2h(self, a, d):
         self._chk(self.L.kmc_hip_memcpy_d2h(self.h, 0, a.ctypes.data, d, a.nbytes))
+
+    def out_rec_bytes(self, p):
+        return self.L.kmc_hip_out_rec_bytes(self.C.byref(p))
+
+    def order_database_device(self, p, descs, out_lut_prefix_len, d_out, out_capacity, d_lut_out):
+        n = self.C.c_uint64()
+        self._chk(self.L.kmc_hip_order_database_device(self.h, 0, self.C.byref(p), descs, len(descs), out_lut_prefix_len, d_out, out_capacity, d_lut_out, self.C.byref(n)))
+        return n.value
 
     def db_set_op_device(self, kmer_len, a, b, op, d_out, out_capacity, d_lut_out):
         C = self.C

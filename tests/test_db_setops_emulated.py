@@ -40,12 +40,8 @@ def goldens():
     return out
 
 
-LINE_IDS = [ln[0] for ln in S.LINES]
-
-
 # ---- 1: the restatement is the reference
-@pytest.mark.parametrize("k", S.PAIRS)
-@pytest.mark.parametrize("line", S.LINES, ids=LINE_IDS)
+@pytest.mark.parametrize("k,line", S.GOLDEN_CASES, ids=S.GOLDEN_IDS)
 def test_the_restatement_writes_what_kmc_tools_writes(goldens, k, line):
     (a, b), (da, db_) = goldens[k]
     r = S.resolve_line(line, S.header_of(a), S.header_of(b))
@@ -65,8 +61,7 @@ def test_the_output_counter_size_is_the_writers(lib):
 
 
 # ---- 2: the device call is the restatement
-@pytest.mark.parametrize("k", S.PAIRS)
-@pytest.mark.parametrize("line", S.LINES, ids=LINE_IDS)
+@pytest.mark.parametrize("k,line", S.GOLDEN_CASES, ids=S.GOLDEN_IDS)
 def test_device_call_on_the_golden_inputs(lib, goldens, k, line):
     (a, b), _ = goldens[k]
     r = S.resolve_line(line, S.header_of(a), S.header_of(b))
@@ -79,11 +74,12 @@ def test_device_call_on_the_golden_inputs(lib, goldens, k, line):
     assert st == wst
 
 
-@pytest.mark.parametrize("k", [27, 32, 55, 127])
-def test_device_call_on_planted_databases(lib, k):
-    """SIZE 1 (k = 27, 32), 2 (55) and 4 (127); databases of 3-4 merge tiles"""
-    cases = S.planted_cases(k, TILE)
-    assert len(cases) > 40
+@pytest.mark.parametrize("k,prefix_lens,reduced", S.PLANTED, ids=S.PLANTED_IDS)
+def test_device_call_on_planted_databases(lib, k, prefix_lens, reduced):
+    """every record width, SIZE 1 (k = 27, 32, 33) .. 7 (193, 224), and at k = 33, 35, 65, 129, 161, 193 the LUT prefix of A, of B and of the output across a 64-bit
+    word boundary; databases of 3-4 merge tiles. The k this test was first written for run every case, the others the reduced list (setops_cases.REDUCED)"""
+    cases = S.planted_cases(k, TILE, prefix_lens=prefix_lens, reduced=reduced)
+    assert len(cases) == 16 if reduced else len(cases) > 40
     seen = dict(n_pairs=0, n_only_a=0, n_only_b=0, n_below_min=0, n_above_max=0, n_written=0)
     for name, a, b, kw in cases:
         try:
@@ -93,6 +89,36 @@ def test_device_call_on_planted_databases(lib, k):
         for key in seen:
             seen[key] += st[key]
     assert all(v > 0 for v in seen.values()), seen  # every tally was exercised
+
+
+@pytest.mark.parametrize("k,prefix_lens,reduced", S.PLANTED, ids=S.PLANTED_IDS)
+def test_the_planted_lists_exercise_every_tally(k, prefix_lens, reduced):
+    """the restatement alone, for the merge tile of this file and for the device's (test_gpu_db_setops.py asserts nothing about the tallies' sum)"""
+    for tile in (TILE, 256 * max(1, 8 // ((k + 31) // 32 + 1))):
+        seen = dict(n_pairs=0, n_only_a=0, n_only_b=0, n_below_min=0, n_above_max=0, n_written=0)
+        for _, a, b, kw in S.planted_cases(k, tile, prefix_lens=prefix_lens, reduced=reduced):
+            cb_a, cb_b = kw["a_fmt"][1], kw["b_fmt"][1]
+            st = S.restate((a[0], [c & ((1 << (8 * cb_a)) - 1) for c in a[1]]), (b[0], [c & ((1 << (8 * cb_b)) - 1) for c in b[1]]), kw.get("a_cut", (1, S.U32)), kw.get("b_cut", (1, S.U32)),
+                           kw["op"], kw["oc"], kw.get("ci", 1), kw.get("cx", S.U32), kw.get("cs", S.U32))[2]
+            for key in seen:
+                seen[key] += st[key]
+        assert all(v > 0 for v in seen.values()), (tile, seen)
+
+
+@pytest.mark.parametrize("k,prefix_lens", S.SEAMS, ids=S.SEAM_IDS)
+def test_cut_records_on_every_tile_seam(lib, k, prefix_lens):
+    """equal key sets in both parities, one side or the other cut by its INPUT'S cutoffs at every position: so_step's pair-or-single decision from the halo record"""
+    cases = S.seam_cut_cases(k, TILE, prefix_lens)
+    assert len(cases) == 32
+    cut = 0
+    for name, a, b, kw in cases:
+        try:
+            st = S.check_case(lib, k, a, b, **kw)
+        except AssertionError as e:
+            raise AssertionError(f"{name}: {e}")
+        assert st["n_pairs"] + st["n_only_a"] + st["n_only_b"] > 0
+        cut += len(a[0]) + len(b[0]) - 2 * st["n_pairs"] - st["n_only_a"] - st["n_only_b"]
+    assert cut >= 32 * (len(cases[0][1][0]) - 1)  # in every case about half of all records are cut
 
 
 # ---- 3: errors
@@ -152,7 +178,7 @@ def test_the_binding_knows_the_entry_point():
 # ---- 4: the front end
 @pytest.mark.parametrize("k", S.PAIRS)
 def test_dbio_round_trips_a_golden_database(k, tmp_path):
-    for name in ("a", "union", "intersect_ocsum_cs65535"):
+    for name in ("a", "union", "intersect_ocsum_cs65535" if k != 33 else "counters_subtract"):
         d = dbio.read_database(S.golden_path(k, name))
         assert not d.kmc2 and d.kmer_len == k and d.total_kmers * d.rec_bytes == d.recs.size and int(d.lut[-1]) <= d.total_kmers
         out = str(tmp_path / name)
@@ -175,13 +201,13 @@ def _same_files(a, b):
 def test_the_command_line_writes_the_golden_databases(k, tmp_path):
     """every golden line; the lines that share their input options go into one command, as kmc_tools takes them"""
     a, b = S.golden_path(k, "a"), S.golden_path(k, "b")
-    plain = [ln for ln in S.LINES if not ln[1] and not ln[2]]
+    plain = [ln for ln in S.LINES_OF[k] if not ln[1] and not ln[2]]
     args = ["simple", a, b]
     for ln in plain:
         args += [ln[3], str(tmp_path / ln[0]), *ln[4]]
     r = _tools(args)
     assert r.returncode == 0, (r.stdout + r.stderr)[-1500:]
-    for ln in S.LINES:
+    for ln in S.LINES_OF[k]:
         if ln not in plain:
             r = _tools(S.command_line(ln, a, b, str(tmp_path / ln[0])))
             assert r.returncode == 0, (r.stdout + r.stderr)[-1500:]
@@ -205,6 +231,16 @@ def test_the_command_line_names_what_it_refuses(tmp_path):
     r = _tools(["simple", str(tmp_path / "set"), a27, "union", str(tmp_path / "o")])
     assert r.returncode != 0 and "counter size 0" in r.stderr
     assert not os.path.exists(str(tmp_path / "o") + ".kmc_pre")
+
+
+@pytest.mark.parametrize("k", sorted(S.RAW_A))
+def test_the_command_line_orders_a_kmc2_fixture_first(k, tmp_path):
+    """the database as `kmc` wrote it (KMC2, tests/golden/setops_k<k>_raw_a) as first input: ordered on the device, then united with b == the `union` golden"""
+    raw = S.golden_path(k, S.RAW_A[k])
+    assert dbio.read_database(raw).kmc2
+    r = _tools(["simple", raw, S.golden_path(k, "b"), "union", str(tmp_path / "u")])
+    assert r.returncode == 0, (r.stdout + r.stderr)[-1500:]
+    _same_files(str(tmp_path / "u"), S.golden_path(k, "union"))
 
 
 def test_the_command_line_orders_a_kmc2_input_first(ref_bins, tmp_path):

@@ -32,7 +32,7 @@ def goldens():
 @pytest.mark.parametrize("k", S.PAIRS)
 def test_device_call_on_the_golden_inputs(ctx, goldens, k):
     (a, b), decoded = goldens[k]
-    for line in S.LINES:
+    for line in S.LINES_OF[k]:
         r = S.resolve_line(line, S.header_of(a), S.header_of(b))
         lut, recs, st = S.run_device(ctx, k, (a.lut_prefix_len, a.counter_size, a.lut, a.recs), (b.lut_prefix_len, b.counter_size, b.lut, b.recs), r["a_cut"], r["b_cut"],
                                      r["op"], r["oc"], r["ci"], r["cx"], r["cs"], r["p_out"])
@@ -42,14 +42,39 @@ def test_device_call_on_the_golden_inputs(ctx, goldens, k):
         assert st == wst, line[0]
 
 
-@pytest.mark.parametrize("k", [27, 32, 55, 127])
-def test_device_call_on_planted_databases(ctx, k):
-    """3-4 product tiles; A == B in both parities (equal_*, equal_shifted_*)"""
-    for name, a, b, kw in S.planted_cases(k, product_tile(k)):
+@pytest.mark.parametrize("k,prefix_lens,reduced", S.PLANTED, ids=S.PLANTED_IDS)
+def test_device_call_on_planted_databases(ctx, k, prefix_lens, reduced):
+    """3-4 product tiles; A == B in both parities (equal_*, equal_shifted_*); every record width (SIZE 1..7) and the LUT prefix of A, of B and of the output across a
+    64-bit word boundary (setops_cases.PLANTED)"""
+    seen = dict(n_pairs=0, n_only_a=0, n_only_b=0, n_below_min=0, n_above_max=0, n_written=0)
+    for name, a, b, kw in S.planted_cases(k, product_tile(k), prefix_lens=prefix_lens, reduced=reduced):
+        try:
+            st = S.check_case(ctx, k, a, b, **kw)
+        except AssertionError as e:
+            raise AssertionError(f"{name}: {e}")
+        for key in seen:
+            seen[key] += st[key]
+    assert all(v > 0 for v in seen.values()), seen  # every tally was exercised
+
+
+@pytest.mark.parametrize("k,prefix_lens", S.SEAMS, ids=S.SEAM_IDS)
+def test_cut_records_on_every_tile_seam(ctx, k, prefix_lens):
+    """equal key sets in both parities, one side or the other cut by its INPUT'S cutoffs at every position, at the product tile (setops_cases.seam_cut_cases)"""
+    for name, a, b, kw in S.seam_cut_cases(k, product_tile(k), prefix_lens):
         try:
             S.check_case(ctx, k, a, b, **kw)
         except AssertionError as e:
             raise AssertionError(f"{name}: {e}")
+
+
+@pytest.mark.parametrize("k", sorted(S.RAW_A))
+def test_the_command_line_orders_a_kmc2_fixture_first(k, tmp_path):
+    """the database as `kmc` wrote it (KMC2) as first input: ordered on the device, then united with b == the `union` golden"""
+    r = subprocess.run([sys.executable, "-m", "kmc_amd.tools", "simple", S.golden_path(k, S.RAW_A[k]), S.golden_path(k, "b"), "union", str(tmp_path / "u")], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-1500:]
+    for ext in (".kmc_pre", ".kmc_suf"):
+        assert open(str(tmp_path / "u") + ext, "rb").read() == open(S.golden_path(k, "union") + ext, "rb").read(), ext
 
 
 def _body27(kmers, counts):

@@ -999,33 +999,7 @@ def read_kmc1_database(db):
     return p, lut.copy(), suf.copy()
 
 
-def order_database_on_device(ctx, hparams, bins, p_out):
-    """bins: [(record bytes, LUT counts)] -> (records bytes, LUT) of kmc_hip_order_database_device"""
-    rb = ctx.out_rec_bytes(hparams)
-    n = len(bins)
-    descs = (capi.BinDesc * n)()
-    allocs = []
-    total = 0
-    for i, (recs, lut) in enumerate(bins):
-        d_out, d_lut, d_small = ctx.malloc(recs.size + 256), ctx.malloc(lut.nbytes), ctx.malloc(64)
-        if recs.size:
-            ctx.h2d(d_out, recs)
-        ctx.h2d(d_lut, lut)
-        ctx.h2d(d_small, np.array([0, 0, 0, 0, recs.size, 0, 0, 0], dtype=np.uint64))
-        allocs += [d_out, d_lut, d_small]
-        descs[i] = capi.BinDesc(0, 0, 0, 0, 0, d_out, recs.size, d_small + 32, d_lut, d_small)
-        total += recs.size // rb
-    rb_out = (hparams.kmer_len - p_out) // 4 + (rb - (hparams.kmer_len - hparams.lut_prefix_len) // 4)
-    d_res, d_lut_out = ctx.malloc(total * rb_out + 256), ctx.malloc(8 << (2 * p_out))
-    got_n = ctx.order_database_device(hparams, descs, p_out, d_res, total * rb_out, d_lut_out)
-    out = np.zeros(got_n * rb_out, dtype=np.uint8)
-    lut = np.zeros(1 << (2 * p_out), dtype=np.uint64)
-    if out.size:
-        ctx.d2h(out, d_res)
-    ctx.d2h(lut, d_lut_out)
-    for a in allocs + [d_res, d_lut_out]:
-        ctx.free(a)
-    return out, lut, got_n
+from order_cases import order_database_on_device  # noqa: E402  (shared with the planted-bin tests of tests/test_order_db_emulated.py / test_gpu_order_db.py)
 
 
 @pytest.mark.parametrize("flags", [["-k27"], ["-k55", "-ci1", "-cs1000"], ["-k21", "-b"]], ids=lambda f: "".join(f))
