@@ -26,7 +26,7 @@ extern "C" {
 #endif
 
 #define KMC_HIP_ABI_VERSION 4 /* 3: + kmc_hip_process_bins_submit/_wait (bound by the worker's loader), kmc_hip_process_bin_multi, kmc_hip_order_database_device;
-                               * 4: kmc_hip_split_params.part_kind (long-read parts) */
+                               * 4: kmc_hip_split_params.part_kind (long-read parts); symbols added since keep it: kmc_hip_db_set_op_device, kmc_hip_db_query_reads_device */
 
 enum {
 	KMC_HIP_OK = 0,
@@ -245,6 +245,34 @@ typedef struct kmc_hip_db_op {
 } kmc_hip_db_op;
 int kmc_hip_db_set_op_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *a, const kmc_hip_db_view *b, const kmc_hip_db_op *op, uint8_t *d_out,
                              uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers, uint64_t stats[6]);
+
+/* ---- reads against an ordered database -----------------------------------------------------------
+ * `kmc_tools filter <db> <reads> <out>` on the device: for every window of kmer_len symbols of every read, the counter the database holds for it. `db` is a database
+ * body as above (its [cutoff_min, cutoff_max]: the database's -ci / -cx; counter_size 1..4), kmer_len <= 224. d_seq[n_bytes] holds the reads' sequence lines as they
+ * are in the file, every read followed by ONE terminator byte ('\n'): read r is d_seq[d_read_off[r] .. d_read_off[r + 1] - 1), d_read_off has n_reads + 1 ascending
+ * entries and the last one is at most n_bytes. Symbols are classified as CKmerAPI::num_codes does (kmc_api/kmer_api.h:268-275): ACGTacgt are 0..3, every other byte —
+ * the terminator too — is invalid, so no window reaches from one read into the next.
+ *   d_counters[i], i < n_bytes (required): the counter of the k-mer that starts at byte i — with both_strands the smaller of it and its reverse complement
+ *     (kmc_file.cpp:998-1001), found by a binary search of the suffix records under the bounds of its LUT prefix (kmc_file.cpp:905-925,1321-1399) — if that counter lies
+ *     in [cutoff_min, cutoff_max]; 0 if the k-mer is absent, cut, the window holds an invalid symbol, or i > n_bytes - kmer_len. Every entry is written.
+ *   d_n_valid[r] (or NULL): the non-zero counters among the read's max(len - kmer_len + 1, 0) windows (fastq_filter.cpp:111-115).
+ *   d_trim_len[r] (or NULL): 0 if len < kmer_len or the first window's counter is below `threshold`; otherwise kmer_len - 1 + j, j the first window >= 1 whose counter
+ *     is below `threshold`, or the number of windows (fastq_filter.cpp:134-152; there a read shorter than kmer_len reads an empty vector).
+ *   d_masked[n_bytes] (or NULL): d_seq with every base of a read replaced by 'N' that lies in a window of that read whose counter is below `threshold`
+ *     (fastq_filter.cpp:153-176); reads shorter than kmer_len, terminators and bytes outside every read are copied.
+ *   stats[0..3]: windows without an invalid symbol; of those, found with a counter inside the cutoffs; found but cut by the cutoffs; windows with an invalid symbol —
+ *     the last counted over the n_bytes - kmer_len + 1 window starts of d_seq, terminators included.
+ * A read must be shorter than 2^32 symbols. Synchronous. An empty database, n_bytes < kmer_len and n_reads == 0 are legal (every counter 0; without reads d_masked is a copy).
+ * KMC_HIP_EINVAL: a NULL argument (d_read_off may be NULL only when n_reads is 0 and none of d_n_valid, d_trim_len, d_masked is given), a counter_size outside 1..4,
+ * a lut_prefix_len with (kmer_len - lut_prefix_len) % 4 != 0, kmer_len > 224; KMC_HIP_ECORRUPT: a LUT whose last entry exceeds n_recs, read offsets that do not ascend
+ * or end behind n_bytes, a read whose terminator is a valid symbol (the outputs are then undefined, nothing outside them is touched).
+ * Replaces: CKMCFile::GetCountersForRead (kmc_api/kmc_file.cpp:873-1027) per read and the three rules of CFastqFilter (kmc_tools/fastq_filter.cpp:106-176), one
+ * thread per input part there. */
+enum { KMC_HIP_DBQ_STAT_VALID = 0, KMC_HIP_DBQ_STAT_FOUND = 1, KMC_HIP_DBQ_STAT_CUT = 2, KMC_HIP_DBQ_STAT_INVALID = 3 };
+int kmc_hip_db_query_reads_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_db_view *db, uint32_t kmer_len, uint32_t both_strands, const uint8_t *d_seq, uint64_t n_bytes,
+                                  const uint64_t *d_read_off, uint64_t n_reads, uint32_t threshold, uint32_t *d_counters /* [n_bytes], required */,
+                                  uint32_t *d_n_valid /* [n_reads] or NULL */, uint32_t *d_trim_len /* [n_reads] or NULL */, uint8_t *d_masked /* [n_bytes] or NULL */,
+                                  uint64_t stats[4]);
 
 /* ---- end-of-run tallies ---------------------------------------------------------------------- */
 

@@ -104,6 +104,7 @@ class DbOp(C.Structure):
 DB_OPS = {"intersect": 0, "union": 1, "kmers_subtract": 2, "counters_subtract": 3, "reverse_kmers_subtract": 4, "reverse_counters_subtract": 5}
 DB_COUNTER_OPS = {"min": 0, "max": 1, "sum": 2, "diff": 3, "left": 4, "right": 5}
 DB_STATS = ("n_pairs", "n_only_a", "n_only_b", "n_below_min", "n_above_max", "n_written")  # stats[] of kmc_hip_db_set_op_device, in order
+DBQ_STATS = ("n_valid_windows", "n_found", "n_cut", "n_invalid_windows")  # stats[] of kmc_hip_db_query_reads_device, in order
 
 
 def make_params(k, both_strands=1, cutoff_min=2, cutoff_max=10**9, counter_max=255, lut_prefix_len=3, output_type=0,
@@ -126,7 +127,7 @@ SYMBOLS = [
     "kmc_hip_split_reads_plan", "kmc_hip_split_reads_emit", "kmc_hip_split_reads_free",
     "kmc_hip_split_set_map", "kmc_hip_split_part", "kmc_hip_split_covers", "kmc_hip_estimate_open", "kmc_hip_estimate_read", "kmc_hip_estimate_close",
     "kmc_hip_smallk_open", "kmc_hip_smallk_part", "kmc_hip_smallk_read", "kmc_hip_smallk_close",
-    "kmc_hip_db_set_op_device",
+    "kmc_hip_db_set_op_device", "kmc_hip_db_query_reads_device",
 ]
 
 _LIB = None
@@ -218,6 +219,8 @@ def load():
         L.kmc_hip_smallk_close.argtypes = [vp, C.c_int]
     if hasattr(L, "kmc_hip_db_set_op_device"):  # added within ABI version 4
         L.kmc_hip_db_set_op_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.POINTER(DbView), C.POINTER(DbOp), vp, C.c_uint64, vp, u64p, u64p]
+    if hasattr(L, "kmc_hip_db_query_reads_device"):  # added within ABI version 4
+        L.kmc_hip_db_query_reads_device.argtypes = [vp, C.c_int, C.POINTER(DbView), C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, u64p]
     _LIB = L
     return L
 
@@ -458,6 +461,17 @@ class Context:
         st = (C.c_uint64 * 6)()
         self._chk(self.L.kmc_hip_db_set_op_device(self.h, dev, kmer_len, C.byref(a), C.byref(b), C.byref(op), d_out, out_capacity, d_lut_out, C.byref(n), st))
         return n.value, dict(zip(DB_STATS, (int(x) for x in st)))
+
+    def db_query_reads_device(self, db: DbView, kmer_len: int, both_strands: bool, d_seq: int, n_bytes: int, d_read_off: int, n_reads: int, threshold: int, d_counters: int,
+                              d_n_valid: int = 0, d_trim_len: int = 0, d_masked: int = 0, dev: int = 0) -> dict:
+        """The reads in d_seq against a device-resident KMC1 body (kmc_hip_db_query_reads_device): fills d_counters[n_bytes] and, where given, d_n_valid[n_reads],
+        d_trim_len[n_reads], d_masked[n_bytes]; returns the dict of the four tallies."""
+        if not hasattr(self.L, "kmc_hip_db_query_reads_device"):
+            raise KmcHipError(-1, f"{lib_path()} has no kmc_hip_db_query_reads_device")
+        st = (C.c_uint64 * 4)()
+        self._chk(self.L.kmc_hip_db_query_reads_device(self.h, dev, C.byref(db), kmer_len, 1 if both_strands else 0, d_seq or None, n_bytes, d_read_off or None, n_reads, threshold,
+                                                       d_counters or None, d_n_valid or None, d_trim_len or None, d_masked or None, st))
+        return dict(zip(DBQ_STATS, (int(x) for x in st)))
 
     def host_alloc(self, nbytes: int) -> np.ndarray:
         """Pinned host memory as a uint8 array (free with host_free(arr))."""

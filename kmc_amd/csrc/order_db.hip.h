@@ -342,4 +342,264 @@ __global__ void __launch_bounds__(SO_THREADS) k_so_tile(const u64 *__restrict__ 
 		go[g] = s_out[g];
 }
 
+/* ---- reads against an ordered database (`kmc_tools filter`) ---- */
+
+#ifndef DQ_THREADS
+#define DQ_THREADS 256 /* threads of a k_dbq_lookup workgroup */
+#endif
+/* window starts per thread of k_dbq_lookup: the tile is DQ_THREADS x this many positions and stages tile + k - 1 symbols, so the halo is read (k - 1) / tile times
+ * too often — 11 % at k = 224 with 2048 positions. LDS is 3 bits per staged symbol: no limit in practice. $KMC_HIP_QUERY_IPT overrides (tests: 1). */
+constexpr u32 DQ_IPT_MAX = 64;
+template <int SIZE> constexpr u32 dq_default_ipt() { return SIZE <= 2 ? 4u : 8u; }
+constexpr u32 dq_staged_symbols(u32 ipt, u32 k) { return (DQ_THREADS * ipt + k - 1 + DQ_THREADS - 1) / DQ_THREADS * DQ_THREADS; } /* whole rows of DQ_THREADS symbols */
+constexpr u32 DQ_CODE_PAD = 2; /* zero words in front of the codes: dq_bits64 reads up to two words before the first symbol */
+constexpr u32 dq_code_words(u32 ipt, u32 k) { return DQ_CODE_PAD + dq_staged_symbols(ipt, k) / 16 + 1; }
+constexpr size_t dq_lds_bytes(u32 ipt, u32 k) { return ((size_t)dq_code_words(ipt, k) + dq_staged_symbols(ipt, k) / 32) * 4; }
+enum : u32 { DQ_ST_VALID = 0, DQ_ST_FOUND = 1, DQ_ST_CUT = 2, DQ_ST_INVALID = 3 };
+
+/* CKmerAPI::num_codes (kmc_api/kmer_api.h:268-275): ACGTacgt -> 0..3, every other byte 4 */
+__device__ __forceinline__ u32 dq_code(u32 c)
+{
+	const u32 u = c & 0xDFu;
+	return u == 'A' ? 0u : u == 'C' ? 1u : u == 'G' ? 2u : u == 'T' ? 3u : 4u;
+}
+
+/* the 64 bits in front of bit `e` of the staged code stream (symbol s: bits 2s, 2s + 1, the first symbol in the most significant bits of word DQ_CODE_PAD) */
+__device__ __forceinline__ u64 dq_bits64(const u32 *code, u32 e)
+{
+	const u32 g = DQ_CODE_PAD + (e >> 5), r = e & 31;
+	const u64 ab = ((u64)code[g - 2] << 32) | code[g - 1];
+	return r ? (ab << r) | (code[g] >> (32 - r)) : ab;
+}
+
+/* flat over the window starts i of d_seq: the k-mer at i (the smaller of it and its reverse complement with both_strands, kmc_file.cpp:998-1001) looked up as
+ * CKMCFile::BinarySearch does under the bounds of its LUT prefix (kmc_file.cpp:905-925,1321-1399) */
+template <int SIZE>
+__global__ void __launch_bounds__(DQ_THREADS) k_dbq_lookup(const uint8_t *__restrict__ seq, u64 n_bytes, u32 k, u32 both_strands, const uint8_t *__restrict__ recs, u64 n_recs,
+                                                          const u64 *__restrict__ lut, u32 p, u32 cbytes, u32 cut_min, u64 cut_max, u32 ipt, u32 *__restrict__ counters /* [n_bytes] */,
+                                                          u64 *__restrict__ stats /* [4] */)
+{
+	KMC_DYN_LDS(u32, dq_lds);
+	__shared__ u32 s_tally[DQ_THREADS / 64][4];
+	const u32 tid = threadIdx.x, lane = tid & 63, tile = DQ_THREADS * ipt, n_sym = dq_staged_symbols(ipt, k);
+	u32 *s_code = dq_lds, *s_inv = dq_lds + dq_code_words(ipt, k);
+	const u64 base = (u64)blockIdx.x * tile;
+	if (tid < DQ_CODE_PAD)
+		s_code[tid] = 0;
+	if (tid == DQ_CODE_PAD)
+		s_code[DQ_CODE_PAD + n_sym / 16] = 0; /* the word dq_bits64 names, and does not use, for a window that ends with the staged symbols */
+	for (u32 row = 0; row < n_sym; row += DQ_THREADS) { /* one coalesced byte per lane; a wave packs its 64 symbols into 4 code words and 2 mask words */
+		const u64 pos = base + row + tid;
+		const u32 c = pos < n_bytes ? dq_code(seq[pos]) : 4u;
+		const u64 inv = __ballot(c > 3);
+		u32 w = (c & 3u) << (30 - 2 * (lane & 15));
+#pragma unroll
+		for (int o = 1; o < 16; o <<= 1)
+			w |= __shfl_down(w, o); /* lanes 0, 16, 32, 48: the OR over their 16 */
+		if ((lane & 15) == 0)
+			s_code[DQ_CODE_PAD + (row + tid) / 16] = w;
+		if (lane == 0) {
+			s_inv[(row + tid) / 32] = (u32)inv;
+			s_inv[(row + tid) / 32 + 1] = (u32)(inv >> 32);
+		}
+	}
+	__syncthreads();
+	const u32 sbytes = (k - p) / 4, rb = sbytes + cbytes, hb = sbytes < 8 ? sbytes : 8;
+	const u64 n_pref = 1ull << (2 * p);
+	u32 tally[4] = {0, 0, 0, 0};
+	for (u32 it = 0; it < ipt; ++it) {
+		const u32 o = it * DQ_THREADS + tid;
+		const u64 i = base + o;
+		if (i >= n_bytes)
+			continue;
+		u32 cnt = 0;
+		if (i + k <= n_bytes) {
+			u32 bad = 0;
+			const u32 g0 = o >> 5, g1 = (o + k - 1) >> 5;
+			for (u32 g = g0; g <= g1; ++g) {
+				u32 m = s_inv[g];
+				if (g == g0)
+					m &= ~0u << (o & 31);
+				if (g == g1)
+					m &= (2u << ((o + k - 1) & 31)) - 1u;
+				bad |= m;
+			}
+			if (bad)
+				++tally[DQ_ST_INVALID];
+			else {
+				++tally[DQ_ST_VALID];
+				u64 x[SIZE];
+#pragma unroll
+				for (int w = 0; w < SIZE; ++w)
+					x[w] = 64u * w < 2 * k ? dq_bits64(s_code, 2 * (o + k) - 64u * w) : 0; /* 2 (o + k) - 64 w > 2 o >= 0 */
+				kmc_mask_low<SIZE>(x, 2 * k);
+				if (both_strands) {
+					u64 rc[SIZE];
+					kmc_revcomp<SIZE>(x, k, rc);
+					if (!kmc_less<SIZE>(x, rc)) { /* kmer < kmer_rev ? kmer : kmer_rev */
+#pragma unroll
+						for (int w = 0; w < SIZE; ++w)
+							x[w] = rc[w];
+					}
+				}
+				const u64 pref = kmc_remove_suffix<SIZE>(x, 2 * (k - p)) & (n_pref - 1);
+				u64 hi = pref + 1 < n_pref ? lut[pref + 1] : n_recs, lo = lut[pref];
+				hi = hi < n_recs ? hi : n_recs; /* a LUT that does not ascend finds nothing; it cannot lead outside the records */
+				lo = lo < hi ? lo : hi;
+				/* the first hb suffix bytes as one number, then byte by byte */
+				u64 head = kmc_remove_suffix<SIZE>(x, 8 * (sbytes - hb));
+				if (hb < 8)
+					head &= (1ull << (8 * hb)) - 1;
+				while (lo < hi) {
+					const u64 mid = (lo + hi) >> 1;
+					const uint8_t *r = recs + mid * rb;
+					u64 rh = 0;
+					for (u32 q = 0; q < hb; ++q)
+						rh = (rh << 8) | r[q];
+					int cmp = rh < head ? -1 : rh > head ? 1 : 0;
+					for (u32 q = hb; cmp == 0 && q < sbytes; ++q) {
+						const u32 pb = sbytes - 1 - q;
+						u32 kb = 0;
+#pragma unroll
+						for (int w = 0; w < SIZE; ++w)
+							if ((pb >> 3) == (u32)w)
+								kb = (u32)(x[w] >> ((pb & 7) * 8)) & 0xFFu;
+						cmp = r[q] < kb ? -1 : r[q] > kb ? 1 : 0;
+					}
+					if (cmp == 0) {
+						u32 c = 0;
+						for (u32 q = 0; q < cbytes; ++q)
+							c |= (u32)r[sbytes + q] << (8 * q);
+						if (c >= cut_min && (u64)c <= cut_max) {
+							cnt = c;
+							++tally[DQ_ST_FOUND];
+						} else
+							++tally[DQ_ST_CUT];
+						break;
+					}
+					if (cmp < 0)
+						lo = mid + 1;
+					else
+						hi = mid;
+				}
+			}
+		}
+		counters[i] = cnt;
+	}
+#pragma unroll
+	for (int q = 0; q < 4; ++q) {
+		const u32 v = wave_sum<u32>(tally[q]);
+		if (lane == 0)
+			s_tally[tid >> 6][q] = v;
+	}
+	__syncthreads();
+	if (tid < 4) {
+		u32 v = 0;
+		for (u32 w = 0; w < DQ_THREADS / 64; ++w)
+			v += s_tally[w][tid];
+		if (v)
+			atomicAdd(stats + tid, (u64)v);
+	}
+}
+
+/* The per-read results, from the counters and the read offsets alone. Reads may be empty or megabases long, so nothing here walks a read: the counters become two bit
+ * arrays with a count per 64 positions (PHASE 0), k_db_cumsum turns the counts into prefix sums, and with those a read's non-zero counters are a difference of two sums and
+ * its first low window a bisection (PHASE 1: one thread per read, which also checks the read's offsets and terminator), and a base is masked when one of the at most k
+ * windows over it — a few words of the bit array — is low (PHASE 2: one thread per byte, its read found by bisection in the offsets).
+ *   0: nz_bits / low_bits[c] bit b = counters[64 c + b] != 0 / < threshold, nz_cnt / low_cnt[c] their population
+ *   1: n_valid[r], trim_len[r] (either may be nullptr); KERR_CORRUPT for offsets that do not ascend, end behind n_bytes, or a terminator that is a valid symbol
+ *   2: masked[i] */
+__device__ __forceinline__ u64 dq_rank(const u64 *__restrict__ sums, const u64 *__restrict__ bits, u64 pos) /* set bits in front of position pos, pos <= n_bytes */
+{
+	const u64 c = pos >> 6;
+	return (pos & 63) ? sums[c] + (u64)__popcll(bits[c] & ((1ull << (pos & 63)) - 1)) : sums[c];
+}
+template <int PHASE>
+__global__ void __launch_bounds__(256) k_dbq_reads(const uint8_t *__restrict__ seq, u64 n_bytes, u32 k, const u64 *__restrict__ read_off, u64 n_reads, u32 threshold,
+                                                  const u32 *__restrict__ counters, u64 *__restrict__ nz_bits, u64 *__restrict__ low_bits, u64 *__restrict__ nz_cnt,
+                                                  u64 *__restrict__ low_cnt /* PHASE 1, 2: the prefix sums of the counts, [chunks + 1] */, u32 *__restrict__ n_valid,
+                                                  u32 *__restrict__ trim_len, uint8_t *__restrict__ masked, u32 *__restrict__ err)
+{
+	const u64 t = (u64)blockIdx.x * 256 + threadIdx.x, n_chunks = (n_bytes + 63) >> 6;
+	if (PHASE == 0) {
+		if ((t >> 6) >= n_chunks) /* the whole wave */
+			return;
+		const u32 c = t < n_bytes ? counters[t] : 0u;
+		const u64 nz = __ballot(t < n_bytes && c != 0), low = __ballot(t < n_bytes && c < threshold);
+		if ((threadIdx.x & 63) == 0) {
+			nz_bits[t >> 6] = nz;
+			low_bits[t >> 6] = low;
+			nz_cnt[t >> 6] = (u64)__popcll(nz);
+			low_cnt[t >> 6] = (u64)__popcll(low);
+		}
+	} else if (PHASE == 1) {
+		if (t >= n_reads)
+			return;
+		const u64 a = read_off[t], b = read_off[t + 1];
+		u32 nv = 0, tl = 0;
+		if (!(a < b) || b > n_bytes || dq_code(seq[b - 1]) < 4)
+			atomicOr(err, KERR_CORRUPT);
+		else if (b - 1 - a >= k) {
+			const u64 n_win = b - a - k; /* len - k + 1 */
+			nv = (u32)(dq_rank(nz_cnt, nz_bits, a + n_win) - dq_rank(nz_cnt, nz_bits, a));
+			if (!((low_bits[a >> 6] >> (a & 63)) & 1)) {
+				/* the first low window behind the read's first: the first set bit at or behind a + 1 — the chunk where the prefix sums pass the rank of a + 1 */
+				const u64 from = a + 1, rank = dq_rank(low_cnt, low_bits, from);
+				u64 j = n_win;
+				if (low_cnt[n_chunks] > rank) {
+					u64 lo = from >> 6, hi = n_chunks - 1; /* smallest chunk c with sums[c + 1] > rank */
+					while (lo < hi) {
+						const u64 mid = (lo + hi) >> 1;
+						if (low_cnt[mid + 1] > rank)
+							hi = mid;
+						else
+							lo = mid + 1;
+					}
+					u64 w = low_bits[lo];
+					if (lo == from >> 6)
+						w &= ~0ull << (from & 63);
+					const u64 at = (lo << 6) + (u64)(__ffsll(w) - 1);
+					j = at - a < n_win ? at - a : n_win;
+				}
+				tl = k - 1 + (u32)j;
+			}
+		}
+		if (n_valid)
+			n_valid[t] = nv;
+		if (trim_len)
+			trim_len[t] = tl;
+	} else {
+		if (t >= n_bytes)
+			return;
+		uint8_t c = seq[t];
+		u64 lo = 0, hi = n_reads + 1; /* offsets <= t */
+		while (lo < hi) {
+			const u64 mid = (lo + hi) >> 1;
+			if (read_off[mid] <= t)
+				lo = mid + 1;
+			else
+				hi = mid;
+		}
+		if (lo >= 1 && lo <= n_reads) {
+			const u64 a = read_off[lo - 1], b = read_off[lo];
+			if (a <= t && t + 1 < b && b <= n_bytes && b - 1 - a >= k) { /* a base of a read of at least k symbols: the windows a + max(j - k + 1, 0) .. a + min(j, n_win - 1) */
+				const u64 j = t - a, n_win = b - a - k;
+				const u64 w0 = a + (j + 1 > k ? j + 1 - k : 0), w1 = a + (j < n_win - 1 ? j : n_win - 1);
+				u64 any = 0;
+				for (u64 g = w0 >> 6; g <= (w1 >> 6); ++g) {
+					u64 m = low_bits[g];
+					if (g == (w0 >> 6))
+						m &= ~0ull << (w0 & 63);
+					if (g == (w1 >> 6))
+						m &= (2ull << (w1 & 63)) - 1;
+					any |= m;
+				}
+				if (any)
+					c = 'N';
+			}
+		}
+		masked[t] = c;
+	}
+}
+
 #endif

@@ -1,14 +1,17 @@
 """python -m kmc_amd.tools simple <db1> [-ci<v> -cx<v>] <db2> [-ci<v> -cx<v>] <operation> <out> [-ci<v> -cx<v> -cs<v> -oc<mode>] [<operation> <out> ...]
+python -m kmc_amd.tools filter [-t | -hm] <db> [-ci<v> -cx<v>] <reads> [-ci<v> -cx<v> -fa|-fq] <out> [-fa|-fq]
 
-`kmc_tools simple` on the device: the argument order and the defaults are the reference's (kmc_tools/parameters_parser.cpp), the databases written are
-byte for byte those kmc_tools writes. One kmc_hip_db_set_op_device call per output; an input as `kmc` wrote it (KMC2) is ordered on the device first."""
+`kmc_tools simple` and `kmc_tools filter` on the device: the argument order and the defaults are the reference's (kmc_tools/parameters_parser.cpp), the databases and
+the reads written are byte for byte those kmc_tools writes. simple: one kmc_hip_db_set_op_device call per output. filter: one kmc_hip_db_query_reads_device call per part
+of the reads file. A database as `kmc` wrote it (KMC2) is ordered on the device first."""
 from __future__ import annotations
 
+import os
 import sys
 
 import numpy as np
 
-from . import capi, dbio
+from . import capi, dbio, readsio
 
 
 class UsageError(SystemExit):
@@ -178,10 +181,228 @@ def simple(argv, ctx=None) -> list:
     return results
 
 
+FILTER_USAGE = """usage: python -m kmc_amd.tools filter [-t | -hm] <db> [-ci<v> -cx<v>] <reads> [-ci<v> -cx<v> -fa|-fq] <out> [-fa|-fq]
+  <db>     -ci / -cx: k-mers with a counter outside [ci, cx] count as absent (default: the database's own cutoffs)
+  <reads>  a FASTQ (default, -fq) or FASTA (-fa) file, '.gz' or not, or @file with one file name per line;
+           -ci / -cx: keep a read with ci <= k-mers found <= cx (defaults 2 and 1e9); with a '.' in the value a fraction [0, 1] of the read's k-mers (both or neither)
+  -t       trim a read behind its last k-mer in front of the first one found fewer than -ci times; -hm: replace every base of such a k-mer by N
+  <out>    -fa writes FASTA from FASTQ
+A read shorter than k has no k-mers: kept like any other read by integer bounds, passed through by -hm, and dropped by -t and by fraction bounds (kmc_tools reads an
+empty vector, or casts a negative number to unsigned, there)."""
+
+
+def _fastq_bound(arg, state):
+    """parameters_parser.cpp:27-56: a value with a '.' is a fraction in [0, 1]; -ci and -cx must be of one kind"""
+    v = arg[3:]
+    if "." in v:
+        try:
+            f = float(v)
+        except ValueError:
+            raise UsageError(f"bad value in {arg}")
+        if not 0.0 <= np.float32(f) <= 1.0:
+            raise UsageError(f"wrong value for fastq input parameter: {arg[:3]}")
+        if state.get("kind") == "int":
+            raise UsageError("both -ci, -cx must be specified as real number [0;1] or as integer")
+        state["kind"] = "float"
+        return np.float32(f)
+    if state.get("kind") == "float":
+        raise UsageError("both -ci, -cx must be specified as real number [0;1] or as integer")
+    state["kind"] = "int"
+    return _num(arg, arg[:3])
+
+
+def parse_filter(argv):
+    """-> dict(mode 'normal' | 'trim' | 'mask', db, db_ci, db_cx (0: not given), inputs [paths], ci, cx, use_float, in_fastq, out, out_fastq)"""
+    pos, mode = 0, "normal"
+    while pos < len(argv) and argv[pos].startswith("-"):  # parameters_parser.cpp:208-226
+        if argv[pos].startswith("-hm"):
+            mode = "mask"
+        elif argv[pos].startswith("-t"):
+            mode = "trim"
+        else:
+            raise UsageError(f"unknown parameter for filter operation: {argv[pos]}")
+        pos += 1
+    if pos >= len(argv):
+        raise UsageError("filter needs an input database\n" + FILTER_USAGE)
+    o = dict(mode=mode, db=argv[pos], db_ci=0, db_cx=0, ci=2, cx=1000000000, f_ci=np.float32(0.0), f_cx=np.float32(1.0), use_float=False, in_fastq=True)
+    pos += 1
+    while pos < len(argv) and argv[pos].startswith("-"):
+        if argv[pos].startswith("-ci"):
+            o["db_ci"] = _num(argv[pos], "-ci")
+        elif argv[pos].startswith("-cx"):
+            o["db_cx"] = _num(argv[pos], "-cx")
+        else:
+            raise UsageError(f"unknown input option {argv[pos]}")
+        pos += 1
+    if pos >= len(argv):
+        raise UsageError("Input fastq files(s) missed")
+    name = argv[pos]
+    pos += 1
+    if name.startswith("@"):
+        try:
+            with open(name[1:]) as f:
+                o["inputs"] = [ln.rstrip("\n") for ln in f if ln.rstrip("\n")]
+        except OSError:
+            raise UsageError(f"No {name[1:]} file")
+    else:
+        o["inputs"] = [name]
+    state = {}
+    while pos < len(argv) and argv[pos].startswith("-"):  # parameters_parser.cpp:129-158
+        a = argv[pos]
+        if a.startswith("-ci"):
+            v = _fastq_bound(a, state)
+            o["f_ci" if state["kind"] == "float" else "ci"] = v
+        elif a.startswith("-cx"):
+            v = _fastq_bound(a, state)
+            o["f_cx" if state["kind"] == "float" else "cx"] = v
+        elif a in ("-fa", "-fq"):
+            o["in_fastq"] = a == "-fq"
+        else:
+            raise UsageError(f"unknown parameter {a}")
+        pos += 1
+    o["use_float"] = state.get("kind") == "float"
+    o["out_fastq"] = o["in_fastq"]
+    if pos >= len(argv):
+        raise UsageError("Output fastq source missed")
+    o["out"] = argv[pos]
+    pos += 1
+    while pos < len(argv):  # parameters_parser.cpp:176-205
+        a = argv[pos]
+        if a in ("-fa", "-fq"):
+            o["out_fastq"] = a == "-fq"
+            if not o["in_fastq"] and o["out_fastq"]:
+                raise UsageError("cannot set -fq for output when -fa is set for input")
+        elif a.startswith("-o"):
+            raise UsageError(f"{a}: KFF is not read or written, only KMC databases")
+        else:
+            raise UsageError(f"Unknown parameter: {a}")
+        pos += 1
+    if o["use_float"] and mode != "normal":
+        raise UsageError("trim (-t) and soft mask (-hm) are not compatibile with float values of cut off (-ci -cx)")
+    return o
+
+
+_LIT = np.frombuffer(b"\n+\n>", dtype=np.uint8)  # the bytes the helpers of fastq_filter.cpp:379-650 write themselves
+
+
+def _filter_part(ctx, view, k, both, o, text) -> tuple:
+    """one part of whole records -> (the bytes kmc_tools writes for it, reads in, reads out, the tallies)"""
+    rec = readsio.parse(text, o["in_fastq"])
+    n = len(rec)
+    seq, off = readsio.sequence_buffer(rec)
+    mode = o["mode"]
+    allocs = []
+
+    def dmalloc(nbytes):
+        allocs.append(ctx.malloc(nbytes + 256))
+        return allocs[-1]
+
+    try:
+        d_seq, d_off, d_cnt = dmalloc(seq.size), dmalloc(off.nbytes), dmalloc(4 * seq.size)
+        d_nv = dmalloc(4 * n) if mode == "normal" else 0
+        d_tl = dmalloc(4 * n) if mode == "trim" else 0
+        d_mk = dmalloc(seq.size) if mode == "mask" else 0
+        if seq.size:
+            ctx.h2d(d_seq, seq)
+        ctx.h2d(d_off, off)
+        st = ctx.db_query_reads_device(view, k, both, d_seq, seq.size, d_off, n, min(o["ci"], 0xFFFFFFFF), d_cnt, d_nv, d_tl, d_mk)
+        res = np.zeros(seq.size if mode == "mask" else n, dtype=np.uint8 if mode == "mask" else np.uint32)  # the per-position counters stay on the device
+        if res.size:
+            ctx.d2h(res, d_nv or d_tl or d_mk)
+    finally:
+        for d in allocs:
+            ctx.free(d)
+    t = rec.text
+    lit = t.size  # the combined source: the text, the helpers' own bytes, the masked sequences
+    nl, nl_plus_nl, gt = (lit, lit + 1), (lit, lit + 3), (lit + 3, lit + 4)
+    src = np.concatenate([t, _LIT, res if mode == "mask" else res[:0].astype(np.uint8)])
+    hs, he = rec.header
+    ss, se = rec.seq
+    length = se - ss
+    fq_out = o["out_fastq"]
+    if mode == "normal":
+        if o["use_float"]:  # fastq_filter.cpp:119-120, float32; a read shorter than k is dropped
+            n_win = np.maximum(length - k + 1, 0)
+            lo, hi = (o["f_ci"] * n_win.astype(np.float32)).astype(np.uint32), (o["f_cx"] * n_win.astype(np.float32)).astype(np.uint32)
+            keep = (res >= lo) & (res <= hi) & (length >= k)
+        else:
+            keep = (res >= o["ci"]) & (res <= o["cx"])
+        if not o["in_fastq"]:
+            segs = [(hs, rec.rec_end)]
+        elif fq_out:  # the quality header's text is dropped
+            segs = [(hs, rec.plus[0] + 1), (rec.plus[1], rec.rec_end)]
+        else:
+            segs = [gt, (hs + 1, rec.plus[0])]
+    elif mode == "trim":
+        keep = res > 0
+        tl = res.astype(np.int64)
+        head = [(hs, he)] if fq_out or not o["in_fastq"] else [gt, (hs + 1, he)]
+        segs = head + [nl, (ss, ss + tl)] + ([nl_plus_nl, (rec.qual[0], rec.qual[0] + tl), nl] if fq_out else [nl])
+    else:
+        keep = np.ones(n, dtype=bool)
+        ms = lit + _LIT.size + off[:-1].astype(np.int64)
+        head = [(hs, he)] if fq_out or not o["in_fastq"] else [gt, (hs + 1, he)]
+        segs = head + [nl, (ms, ms + length)] + ([nl_plus_nl, rec.qual, nl] if fq_out else [nl])
+    sel = np.flatnonzero(keep)
+    col = lambda v: np.full(sel.size, v, dtype=np.int64) if np.isscalar(v) else np.asarray(v, dtype=np.int64)[sel]  # noqa: E731
+    starts = np.stack([col(a) for a, _ in segs], axis=1) if sel.size else np.zeros((0, len(segs)), dtype=np.int64)
+    ends = np.stack([col(b) for _, b in segs], axis=1) if sel.size else starts
+    return readsio.gather(src, starts, ends), n, int(sel.size), st
+
+
+def filter_reads(argv, ctx=None) -> dict:
+    """Runs the command line; returns dict(n_reads, n_written, and the summed tallies of kmc_hip_db_query_reads_device)."""
+    o = parse_filter(argv)
+    if dbio.is_kff(o["db"]) and not os.path.exists(o["db"] + ".kmc_pre"):
+        raise UsageError(f"{o['db']}: a KFF file; only KMC databases are read")
+    try:
+        db = dbio.read_database(o["db"])
+    except (dbio.DbFormatError, OSError) as e:
+        raise UsageError(str(e))
+    if db.counter_size == 0:
+        raise UsageError(f"{o['db']}: counter size 0 (a k-mer set without counters) is not supported")
+    # CKMCFile::SetMinCount / SetMaxCount (kmc_file.cpp:664-698): a bound outside the database's own is ignored; the upper one is taken as 32 bits
+    ci, cx = db.min_count, db.max_count
+    if db.min_count <= o["db_ci"] <= cx:
+        ci = o["db_ci"]
+    if db.max_count >= (o["db_cx"] & 0xFFFFFFFF) >= ci:
+        cx = o["db_cx"] & 0xFFFFFFFF
+    part_bytes = max(1, int(float(os.environ.get("KMC_HIP_FILTER_PART_MB", "64")) * (1 << 20)))
+    own = ctx is None
+    if own:
+        ctx = capi.Context((0,))
+    dev = None
+    total = dict(n_reads=0, n_written=0, **dict.fromkeys(capi.DBQ_STATS, 0))
+    try:
+        dev = _DeviceDb(ctx, db)
+        view = dev.view(ci, cx)
+        with open(o["out"], "wb") as out:
+            for path in o["inputs"]:
+                for text in readsio.parts(path, o["in_fastq"], part_bytes):
+                    try:
+                        data, n_in, n_out, st = _filter_part(ctx, view, db.kmer_len, db.both_strands, o, text)
+                    except readsio.FormatError as e:
+                        raise UsageError(f"{path}: {e}")
+                    out.write(data.tobytes())
+                    total["n_reads"] += n_in
+                    total["n_written"] += n_out
+                    for key in capi.DBQ_STATS:
+                        total[key] += st[key]
+    finally:
+        if dev:
+            dev.free()
+        if own:
+            ctx.close()
+    return total
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
+    if argv and argv[0] == "filter":
+        print(", ".join(f"{a} {b}" for a, b in filter_reads(argv[1:]).items()))
+        return 0
     if not argv or argv[0] != "simple":
-        raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...")
+        raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...\n" + FILTER_USAGE)
     for (o, st) in zip(parse_simple(argv[1:])[1], simple(argv[1:])):
         print(f"{o['op']} -> {o['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
     return 0
