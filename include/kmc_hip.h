@@ -274,6 +274,43 @@ int kmc_hip_db_query_reads_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_db_vi
                                   uint32_t *d_n_valid /* [n_reads] or NULL */, uint32_t *d_trim_len /* [n_reads] or NULL */, uint8_t *d_masked /* [n_bytes] or NULL */,
                                   uint64_t stats[4]);
 
+/* ---- one database transformed -----------------------------------------------------------------------
+ * `kmc_tools transform <db> reduce | compact | set_counts | sort | histogram | dump` on the device (kmc_tools/kmc_tools.cpp:41-137,415-484; the command line and its
+ * defaults: parameters_parser.cpp:272-453,842-892). `db` is a database body as above, kmer_len - lut_prefix_len a positive multiple of 4, counter_size 1..4. A record whose
+ * counter lies outside the view's [cutoff_min, cutoff_max] — the input's -ci / -cx — is absent for every output (kmc1_db_reader.h:574-576,618, kmc2_db_reader.h:1812,1897)
+ * and counted in stats[KMC_HIP_DBT_STAT_CUT_IN]. All three are synchronous; an empty database is legal (d_recs may then be NULL). KMC_HIP_EINVAL: a NULL argument, a
+ * counter_size outside 1..4, a lut_prefix_len that is not as above, an output's cutoff_min or counter_max below 1; KMC_HIP_ECORRUPT: a LUT whose last entry exceeds n_recs.
+ *
+ * _reduce: the database outputs. db is ORDERED (a KMC1 body; kmer_len <= 224). The writer's rule (kmc1_db_writer.h:375-404): with counter_value != 0 (set_counts) every
+ *   present record is written with that count; otherwise a count below cutoff_min or above cutoff_max is dropped and what is left is clamped to counter_max. reduce, compact
+ *   (counter_max 1) and sort of a body that is already ordered are this rule with the command line's numbers. d_out receives the kept records in their order, packed for
+ *   out_lut_prefix_len and a counter of MIN(BYTE_LOG(counter_max), BYTE_LOG(cutoff_max)) bytes — BYTE_LOG(counter_value) for set_counts — (kmc1_db_writer.h:154-156),
+ *   d_lut_out the LUT of 4^out_lut_prefix_len entries, as kmc_hip_db_set_op_device leaves them. out_capacity (bytes) must hold n_recs records: KMC_HIP_ECAPACITY otherwise.
+ *   *n_kmers = records written = stats[KMC_HIP_DBT_STAT_WRITTEN]; stats[1], [2]: present records the output's cutoff_min / cutoff_max dropped.
+ *   Replaces: CKMC1DbWriter<SIZE>::add_kmer fed record by record from the loop of CTools::ProcessTransformOper (kmc_tools.cpp:93-115).
+ * _histogram: d_hist[cutoff_max - cutoff_min + 1] (uint64, every entry written): entry i = present records whose counter is cutoff_min + i, no clamp
+ *   (histogram_writer.h:32-36; the text `i\tcount\n` is the caller's, :45-48). The records need not be ordered: the counters are read straight from the packed records.
+ *   n_lut_segments (>= 1) says how long the LUT is, as for _dump; counting does not read it beyond the check of its end. KMC_HIP_EINVAL also for cutoff_max < cutoff_min or
+ *   >= 2^32. stats[3]: cut by the input, present but outside [cutoff_min, cutoff_max], counted.
+ *   Replaces: CHistogramWriterForTransform::PutCounter per record (kmc_tools.cpp:75-92).
+ * _dump: records [first, first + count) of the body as text into d_text, per record kept `<kmer_len symbols ACGT>\t<decimal counter>\n` (dump_writer.h:111-160): kept
+ *   if cutoff_min <= counter <= cutoff_max, then clamped to counter_max; in record order. n_lut_segments: 1 for an ordered body (a LUT of 4^lut_prefix_len entries); for a
+ *   body as `kmc` wrote it (KMC2: records ordered inside every bin, the bins one after the other) the number of bins — the LUT is then the file's: n_lut_segments x
+ *   4^lut_prefix_len global record offsets and ONE closing entry (= n_recs) behind them, and a record's prefix is the index of the last entry <= its number, modulo
+ *   4^lut_prefix_len (kmc2_db_reader.h:1776-1791) — so a KMC2 database is dumped in file order without ordering it. A record takes at most kmer_len + 12 bytes:
+ *   text_capacity < count x (kmer_len + 12) is KMC_HIP_ECAPACITY. *n_bytes = bytes written; no byte of d_text outside [0, *n_bytes) is touched. count == 0 is legal;
+ *   first + count > n_recs is KMC_HIP_EINVAL. stats[4]: cut by the input, below cutoff_min, above cutoff_max, records written — of the range.
+ *   $KMC_HIP_DUMP_TILE: records per workgroup (default: 32 KiB of text).
+ *   Replaces: CDumpWriterForTransform<SIZE>::PutKmer per record (kmc_tools.cpp:83-103), one thread. */
+enum { KMC_HIP_DBT_STAT_CUT_IN = 0, KMC_HIP_DBT_STAT_BELOW_MIN = 1, KMC_HIP_DBT_STAT_ABOVE_MAX = 2, KMC_HIP_DBT_STAT_WRITTEN = 3 };
+enum { KMC_HIP_DBH_STAT_CUT_IN = 0, KMC_HIP_DBH_STAT_OUTSIDE = 1, KMC_HIP_DBH_STAT_COUNTED = 2 };
+int kmc_hip_db_reduce_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *db, uint32_t cutoff_min, uint64_t cutoff_max, uint32_t counter_max,
+                             uint32_t counter_value, uint32_t out_lut_prefix_len, uint8_t *d_out, uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers, uint64_t stats[4]);
+int kmc_hip_db_histogram_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *db, uint32_t n_lut_segments, uint32_t cutoff_min, uint64_t cutoff_max,
+                                uint64_t *d_hist, uint64_t stats[3]);
+int kmc_hip_db_dump_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *db, uint32_t n_lut_segments, uint64_t first, uint64_t count, uint32_t cutoff_min,
+                           uint64_t cutoff_max, uint32_t counter_max, uint8_t *d_text, uint64_t text_capacity, uint64_t *n_bytes, uint64_t stats[4]);
+
 /* ---- end-of-run tallies ---------------------------------------------------------------------- */
 
 /* Sum stats[4] over the context's devices with one RCCL all-reduce (ncclUint64 x 4, ncclSum) over xGMI.

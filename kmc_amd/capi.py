@@ -105,6 +105,8 @@ DB_OPS = {"intersect": 0, "union": 1, "kmers_subtract": 2, "counters_subtract": 
 DB_COUNTER_OPS = {"min": 0, "max": 1, "sum": 2, "diff": 3, "left": 4, "right": 5}
 DB_STATS = ("n_pairs", "n_only_a", "n_only_b", "n_below_min", "n_above_max", "n_written")  # stats[] of kmc_hip_db_set_op_device, in order
 DBQ_STATS = ("n_valid_windows", "n_found", "n_cut", "n_invalid_windows")  # stats[] of kmc_hip_db_query_reads_device, in order
+DBT_STATS = ("n_cut_in", "n_below_min", "n_above_max", "n_written")  # stats[] of kmc_hip_db_reduce_device and kmc_hip_db_dump_device, in order
+DBH_STATS = ("n_cut_in", "n_outside", "n_counted")  # stats[] of kmc_hip_db_histogram_device, in order
 
 
 def make_params(k, both_strands=1, cutoff_min=2, cutoff_max=10**9, counter_max=255, lut_prefix_len=3, output_type=0,
@@ -128,6 +130,7 @@ SYMBOLS = [
     "kmc_hip_split_set_map", "kmc_hip_split_part", "kmc_hip_split_covers", "kmc_hip_estimate_open", "kmc_hip_estimate_read", "kmc_hip_estimate_close",
     "kmc_hip_smallk_open", "kmc_hip_smallk_part", "kmc_hip_smallk_read", "kmc_hip_smallk_close",
     "kmc_hip_db_set_op_device", "kmc_hip_db_query_reads_device",
+    "kmc_hip_db_reduce_device", "kmc_hip_db_histogram_device", "kmc_hip_db_dump_device",
 ]
 
 _LIB = None
@@ -221,6 +224,10 @@ def load():
         L.kmc_hip_db_set_op_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.POINTER(DbView), C.POINTER(DbOp), vp, C.c_uint64, vp, u64p, u64p]
     if hasattr(L, "kmc_hip_db_query_reads_device"):  # added within ABI version 4
         L.kmc_hip_db_query_reads_device.argtypes = [vp, C.c_int, C.POINTER(DbView), C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, u64p]
+    if hasattr(L, "kmc_hip_db_reduce_device"):  # added within ABI version 4, all three together
+        L.kmc_hip_db_reduce_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, u64p, u64p]
+        L.kmc_hip_db_histogram_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint32, C.c_uint64, vp, u64p]
+        L.kmc_hip_db_dump_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, u64p]
     _LIB = L
     return L
 
@@ -472,6 +479,39 @@ class Context:
         self._chk(self.L.kmc_hip_db_query_reads_device(self.h, dev, C.byref(db), kmer_len, 1 if both_strands else 0, d_seq or None, n_bytes, d_read_off or None, n_reads, threshold,
                                                        d_counters or None, d_n_valid or None, d_trim_len or None, d_masked or None, st))
         return dict(zip(DBQ_STATS, (int(x) for x in st)))
+
+    def _need(self, name):
+        if not hasattr(self.L, name):
+            raise KmcHipError(-1, f"{lib_path()} has no {name}")
+
+    def db_reduce_device(self, kmer_len: int, db: DbView, cutoff_min: int, cutoff_max: int, counter_max: int, counter_value: int, out_lut_prefix_len: int, d_out: int,
+                         out_capacity: int, d_lut_out: int, dev: int = 0):
+        """A database output of `kmc_tools transform` (reduce, compact, set_counts, sort of an ordered body) from a device-resident KMC1 body (kmc_hip_db_reduce_device);
+        returns (records written, dict of the four tallies)."""
+        self._need("kmc_hip_db_reduce_device")
+        n = C.c_uint64()
+        st = (C.c_uint64 * 4)()
+        self._chk(self.L.kmc_hip_db_reduce_device(self.h, dev, kmer_len, C.byref(db), cutoff_min, cutoff_max, counter_max, counter_value, out_lut_prefix_len, d_out or None, out_capacity,
+                                                  d_lut_out or None, C.byref(n), st))
+        return n.value, dict(zip(DBT_STATS, (int(x) for x in st)))
+
+    def db_histogram_device(self, kmer_len: int, db: DbView, n_lut_segments: int, cutoff_min: int, cutoff_max: int, d_hist: int, dev: int = 0) -> dict:
+        """The counters of a device-resident body counted into d_hist[cutoff_max - cutoff_min + 1] (kmc_hip_db_histogram_device); returns the dict of the three tallies."""
+        self._need("kmc_hip_db_histogram_device")
+        st = (C.c_uint64 * 3)()
+        self._chk(self.L.kmc_hip_db_histogram_device(self.h, dev, kmer_len, C.byref(db), n_lut_segments, cutoff_min, cutoff_max, d_hist or None, st))
+        return dict(zip(DBH_STATS, (int(x) for x in st)))
+
+    def db_dump_device(self, kmer_len: int, db: DbView, n_lut_segments: int, first: int, count: int, cutoff_min: int, cutoff_max: int, counter_max: int, d_text: int,
+                       text_capacity: int, dev: int = 0):
+        """Records [first, first + count) of a device-resident body as the text of `kmc_tools transform dump` (kmc_hip_db_dump_device); returns (bytes written, dict of the
+        four tallies)."""
+        self._need("kmc_hip_db_dump_device")
+        n = C.c_uint64()
+        st = (C.c_uint64 * 4)()
+        self._chk(self.L.kmc_hip_db_dump_device(self.h, dev, kmer_len, C.byref(db), n_lut_segments, first, count, cutoff_min, cutoff_max, counter_max, d_text or None, text_capacity,
+                                                C.byref(n), st))
+        return n.value, dict(zip(DBT_STATS, (int(x) for x in st)))
 
     def host_alloc(self, nbytes: int) -> np.ndarray:
         """Pinned host memory as a uint8 array (free with host_free(arr))."""

@@ -428,3 +428,4 @@ int read_and_clear_sticky(Slot &s, u32 &err)
 #include "host_cabi_collective.hip.h" /* the tally all-reduce over the devices of a context (RCCL) and the instrumentation entries */
 #include "host_setops.hip.h" /* set operations between two ordered databases (`kmc_tools simple`) */
 #include "host_query.hip.h" /* the reads of a file against an ordered database (`kmc_tools filter`) */
+#include "host_transform.hip.h" /* one database reduced, histogrammed or dumped as text (`kmc_tools transform`) */

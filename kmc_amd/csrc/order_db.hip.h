@@ -602,4 +602,291 @@ __global__ void __launch_bounds__(256) k_dbq_reads(const uint8_t *__restrict__ s
 	}
 }
 
+/* ---- one database transformed (`kmc_tools transform`: reduce / compact / set_counts / sort, histogram, dump) ----
+ * reduce     k_db_unpack (every record present), k_tr_compact<false> counts the records of every tile the cutoffs keep and the tallies, k_db_cumsum scans the counts,
+ *            k_tr_compact<true> writes the kept records — clamped, or with the count of set_counts — at their offsets (a stable compaction: the order stays), k_db_pack
+ * histogram  k_tr_hist: the counters read straight from the packed records; the bins of a workgroup in LDS while the range fits (equal counters of a wave combined
+ *            before the LDS atomic, one flush per workgroup), 64-bit atomics on the bins in HBM otherwise
+ * dump       k_tr_dump<false> counts the text bytes of every tile, k_db_cumsum scans them, k_tr_dump<true> formats the tile's text into LDS and copies it out */
+#ifndef TR_THREADS
+#define TR_THREADS 256 /* threads of a k_tr_* workgroup */
+#endif
+constexpr u32 TR_REDUCE_IPT = 1;        /* consecutive records per thread of k_tr_compact: a tile is TR_THREADS x this many (1: neighbouring lanes read neighbouring records) */
+/* bins k_tr_hist keeps in LDS: 40 KiB of 32-bit bins, four workgroups (16 waves) on a CU's 160 KiB, and the whole default range of `kmc_tools transform histogram`
+ * (-cx 10000, parameters_parser.cpp:884) */
+constexpr u32 TR_HIST_LDS_BINS = 10240;
+constexpr u32 TR_HIST_PEEL = 2;         /* rounds in which a wave combines the lanes that hold its first active lane's counter; what is left adds lane by lane */
+constexpr u32 TR_HIST_MAX_GROUPS = 1024; /* workgroups of k_tr_hist: each flushes its bins once */
+constexpr u32 TR_IMAGE_BYTES = 32 * 1024; /* a dump tile's text by default: four workgroups on a CU */
+constexpr u32 TR_IMAGE_MAX = 64 * 1024 - 64; /* the most an override may ask for (with the 16 bytes of alignment slack in front) */
+constexpr u32 TR_REC_EXTRA = 12;        /* '\t', ten digits, '\n': a record of the dump is at most kmer_len + 12 bytes */
+enum : u32 { TR_ST_CUT_IN = 0, TR_ST_BELOW_MIN = 1, TR_ST_ABOVE_MAX = 2, TR_ST_WRITTEN = 3 };
+constexpr u32 tr_default_tile(u32 k) { return TR_IMAGE_BYTES / (k + TR_REC_EXTRA) ? TR_IMAGE_BYTES / (k + TR_REC_EXTRA) : 1u; }
+constexpr size_t tr_dump_lds_bytes(u32 tile, u32 k) { return (size_t)tile * (k + TR_REC_EXTRA) + 16; }
+
+struct TrCut {
+	u32 in_min;
+	u64 in_max; /* the input's cutoffs: a record outside them is absent (kmc1_db_reader.h:574-576, kmc2_db_reader.h:1812) */
+	u32 out_min;
+	u64 out_max;
+	u32 counter_max, counter_value; /* of the output; counter_value != 0: set_counts */
+};
+
+/* the readers' and the writers' rule for one counter: 0 kept (c: what is written), TR_ST_CUT_IN + 1, TR_ST_BELOW_MIN + 1, TR_ST_ABOVE_MAX + 1 otherwise
+ * (kmc1_db_writer.h:378-385, dump_writer.h:145-148) */
+__device__ __forceinline__ u32 tr_classify(u32 &c, const TrCut &cut)
+{
+	if (c < cut.in_min || (u64)c > cut.in_max)
+		return TR_ST_CUT_IN + 1;
+	if (cut.counter_value) {
+		c = cut.counter_value;
+		return 0;
+	}
+	if (c < cut.out_min)
+		return TR_ST_BELOW_MIN + 1;
+	if ((u64)c > cut.out_max)
+		return TR_ST_ABOVE_MAX + 1;
+	if (c > cut.counter_max)
+		c = cut.counter_max;
+	return 0;
+}
+
+__device__ __forceinline__ u32 tr_counter(const uint8_t *__restrict__ r, u32 cbytes) /* counter bytes, least significant first */
+{
+	u32 c = 0;
+	for (u32 q = 0; q < cbytes; ++q)
+		c |= (u32)r[q] << (8 * q);
+	return c;
+}
+
+__device__ __forceinline__ void tr_add_tallies(const u32 mine[3], u64 *__restrict__ stats)
+{
+#pragma unroll
+	for (int q = 0; q < 3; ++q) {
+		const u32 v = wave_sum<u32>(mine[q]);
+		if ((threadIdx.x & 63) == 0 && v)
+			atomicAdd(stats + q, (u64)v);
+	}
+}
+
+/* WRITE = false: tile_count[tile] = records of the tile that are kept, stats[0..2] += the tile's tallies. WRITE = true: the kept records, in their order, to
+ * out[tile_base[tile] ..] with the count that is written. */
+template <int SIZE, bool WRITE>
+__global__ void __launch_bounds__(TR_THREADS) k_tr_compact(const u64 *__restrict__ recs /* [n][SIZE + 1] */, u64 n, TrCut cut, const u64 *__restrict__ tile_base, u64 *__restrict__ tile_count,
+                                                          u64 *__restrict__ out, u64 *__restrict__ stats)
+{
+	constexpr int W = SIZE + 1;
+	__shared__ u32 s_scan[TR_THREADS / 64 + 1];
+	const u64 j0 = ((u64)blockIdx.x * TR_THREADS + threadIdx.x) * TR_REDUCE_IPT;
+	u32 kept = 0, keep_bits = 0, cnt[TR_REDUCE_IPT], mine[3] = {0, 0, 0};
+#pragma unroll
+	for (u32 q = 0; q < TR_REDUCE_IPT; ++q) {
+		cnt[q] = 0;
+		if (j0 + q < n) {
+			cnt[q] = (u32)recs[(j0 + q) * W + SIZE];
+			const u32 cls = tr_classify(cnt[q], cut);
+			if (cls)
+				mine[cls - 1] += 1;
+			else {
+				keep_bits |= 1u << q;
+				++kept;
+			}
+		}
+	}
+	u32 total;
+	const u32 first = block_excl_sum<TR_THREADS / 64, u32>(kept, s_scan, total);
+	if (!WRITE) {
+		tr_add_tallies(mine, stats);
+		if (threadIdx.x == 0)
+			tile_count[blockIdx.x] = total;
+		return;
+	}
+	u64 *o = out + (tile_base[blockIdx.x] + first) * W;
+#pragma unroll
+	for (u32 q = 0; q < TR_REDUCE_IPT; ++q)
+		if (keep_bits & (1u << q)) {
+			const u64 *r = recs + (j0 + q) * W;
+#pragma unroll
+			for (int w = 0; w < SIZE; ++w)
+				o[w] = r[w];
+			o[SIZE] = cnt[q];
+			o += W;
+		}
+}
+
+/* hist[c - lo] += 1 for every record whose counter c lies inside the input's cutoffs and in [lo, hi]; stats[0] += cut by the input, [1] += outside [lo, hi], [2] += counted.
+ * LDS_BINS: n_bins <= TR_HIST_LDS_BINS 32-bit bins in dynamic LDS (a workgroup sees fewer than 2^32 records). */
+template <bool LDS_BINS>
+__global__ void __launch_bounds__(TR_THREADS) k_tr_hist(const uint8_t *__restrict__ recs, u64 n, u32 sbytes, u32 cbytes, u32 in_min, u64 in_max, u32 lo, u64 hi, u32 n_bins,
+                                                       u64 *__restrict__ hist, u64 *__restrict__ stats)
+{
+	KMC_DYN_LDS(u32, s_bins);
+	const u32 tid = threadIdx.x, lane = tid & 63;
+	if (LDS_BINS) {
+		for (u32 i = tid; i < n_bins; i += TR_THREADS)
+			s_bins[i] = 0;
+		__syncthreads();
+	}
+	const u64 stride = (u64)gridDim.x * TR_THREADS, rounds = (n + stride - 1) / stride; /* every lane makes every round: the wave votes together */
+	const u32 rb = sbytes + cbytes;
+	u32 mine[3] = {0, 0, 0};
+	for (u64 r = 0; r < rounds; ++r) {
+		const u64 j = r * stride + (u64)blockIdx.x * TR_THREADS + tid;
+		u32 c = 0;
+		bool active = false;
+		if (j < n) {
+			c = tr_counter(recs + j * rb + sbytes, cbytes);
+			if (c < in_min || (u64)c > in_max)
+				mine[0] += 1;
+			else if (c < lo || (u64)c > hi)
+				mine[1] += 1;
+			else {
+				mine[2] += 1;
+				active = true;
+			}
+		}
+		const u32 bin = c - lo;
+		for (u32 peel = 0; peel < TR_HIST_PEEL; ++peel) {
+			const u64 todo = __ballot(active);
+			if (!todo)
+				break;
+			const int leader = __ffsll(todo) - 1;
+			const u32 lbin = __shfl(bin, leader);
+			const u64 same = __ballot(active && bin == lbin);
+			if ((int)lane == leader) {
+				if (LDS_BINS)
+					atomicAdd(s_bins + lbin, (u32)__popcll(same));
+				else
+					atomicAdd(hist + lbin, (u64)__popcll(same));
+			}
+			if (bin == lbin)
+				active = false;
+		}
+		if (active) {
+			if (LDS_BINS)
+				atomicAdd(s_bins + bin, 1u);
+			else
+				atomicAdd(hist + bin, (u64)1);
+		}
+	}
+	tr_add_tallies(mine, stats);
+	if (LDS_BINS) {
+		__syncthreads();
+		for (u32 i = tid; i < n_bins; i += TR_THREADS) {
+			const u32 v = s_bins[i];
+			if (v)
+				atomicAdd(hist + i, (u64)v);
+		}
+	}
+}
+
+struct TrDump {
+	u32 k, p, sbytes, cbytes;
+	u32 n_entries; /* of the LUT: segments x 4^p (a KMC1 body: one segment; a KMC2 body: one per bin, the entries global record offsets) */
+	u32 tile;      /* records of a tile */
+};
+struct __attribute__((aligned(16))) TrVec16 {
+	u64 a, b;
+};
+
+__device__ __forceinline__ u32 tr_digits(u32 v)
+{
+	return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u : v < 10000000u ? 7u : v < 100000000u ? 8u : v < 1000000000u ? 9u : 10u;
+}
+__device__ __forceinline__ uint8_t tr_symbol(u32 x) { return (uint8_t)(0x54474341u >> (8 * (x & 3))); } /* "ACGT" */
+
+/* Records [first, first + count) of the body as text, `<k symbols>\t<decimal counter>\n` per record the cutoffs keep (dump_writer.h:111-160), in record order.
+ * WRITE = false: tile_bytes[tile] = text bytes of the tile, stats[0..2] += its tallies. WRITE = true: the tile's text to text[tile_base[tile] ..). A thread takes
+ * ceil(tile / TR_THREADS) consecutive records; the prefix of its first one is found by bisection of the LUT (the last entry <= the record's number; in a segmented
+ * LUT the prefix is that entry's index modulo 4^p, kmc2_db_reader.h:1776-1791), the following ones by walking on. The text is built in LDS at the byte offset the
+ * tile's first byte has inside its 16 bytes of HBM, so that whole aligned 16-byte pieces go out; the bytes in front of the first piece and behind the last one are
+ * written one by one. Nothing outside text[tile_base[tile] .. tile_base[tile + 1]) is written. */
+template <bool WRITE>
+__global__ void __launch_bounds__(TR_THREADS) k_tr_dump(const uint8_t *__restrict__ recs, const u64 *__restrict__ lut, u64 first, u64 count, TrDump d, TrCut cut, const u64 *__restrict__ tile_base,
+                                                       u64 *__restrict__ tile_bytes, uint8_t *__restrict__ text, u64 *__restrict__ stats)
+{
+	KMC_DYN_LDS(uint8_t, s_img);
+	__shared__ u32 s_scan[TR_THREADS / 64 + 1];
+	const u32 tid = threadIdx.x, ipt = (d.tile + TR_THREADS - 1) / TR_THREADS, rb = d.sbytes + d.cbytes;
+	const u64 l0 = (u64)blockIdx.x * d.tile;
+	const u32 len = (u32)(count - l0 < (u64)d.tile ? count - l0 : (u64)d.tile);
+	const u32 m0 = tid * ipt < len ? tid * ipt : len, m1 = m0 + ipt < len ? m0 + ipt : len;
+	u32 bytes = 0, mine[3] = {0, 0, 0};
+	for (u32 m = m0; m < m1; ++m) {
+		u32 c = tr_counter(recs + (first + l0 + m) * rb + d.sbytes, d.cbytes);
+		const u32 cls = tr_classify(c, cut);
+		if (cls)
+			mine[cls - 1] += 1;
+		else
+			bytes += d.k + 2 + tr_digits(c);
+	}
+	u32 total;
+	u32 off = block_excl_sum<TR_THREADS / 64, u32>(bytes, s_scan, total);
+	if (!WRITE) {
+		tr_add_tallies(mine, stats);
+		if (tid == 0)
+			tile_bytes[blockIdx.x] = total;
+		return;
+	}
+	uint8_t *dst = text + tile_base[blockIdx.x];
+	const u32 mis = (u32)((size_t)dst & 15);
+	uint8_t *img = s_img + mis;
+	if (m0 < m1) {
+		const u64 ja = first + l0 + m0;
+		u32 lo = 0, hi = d.n_entries; /* the last entry <= ja (entry 0 is 0) */
+		while (hi - lo > 1) {
+			const u32 mid = (lo + hi) >> 1;
+			if (lut[mid] <= ja)
+				lo = mid;
+			else
+				hi = mid;
+		}
+		const u32 pmask = (1u << (2 * d.p)) - 1;
+		for (u32 m = m0; m < m1; ++m) {
+			const u64 j = ja + (m - m0);
+#pragma unroll 1
+			while (lo + 1 < d.n_entries && lut[lo + 1] <= j)
+				++lo;
+			const uint8_t *r = recs + j * rb;
+			u32 c = tr_counter(r + d.sbytes, d.cbytes);
+			if (tr_classify(c, cut))
+				continue;
+			uint8_t *o = img + off;
+			const u32 prefix = lo & pmask;
+#pragma unroll 1
+			for (u32 q = 0; q < d.p; ++q)
+				*o++ = tr_symbol(prefix >> (2 * (d.p - 1 - q)));
+#pragma unroll 1
+			for (u32 q = 0; q < d.sbytes; ++q) {
+				const u32 b = r[q];
+				o[0] = tr_symbol(b >> 6);
+				o[1] = tr_symbol(b >> 4);
+				o[2] = tr_symbol(b >> 2);
+				o[3] = tr_symbol(b);
+				o += 4;
+			}
+			*o++ = '\t';
+			const u32 nd = tr_digits(c);
+#pragma unroll 1
+			for (u32 q = nd; q > 0; --q) { /* c / 10 as a multiplication: 0xCCCCCCCD = ceil(2^35 / 10) */
+				const u32 tenth = (u32)(((u64)c * 0xCCCCCCCDull) >> 35);
+				o[q - 1] = (uint8_t)('0' + (c - tenth * 10u));
+				c = tenth;
+			}
+			o[nd] = '\n';
+			off += d.k + 2 + nd;
+		}
+	}
+	__syncthreads();
+	const u32 head = total < ((16u - mis) & 15u) ? total : ((16u - mis) & 15u), n_vec = (total - head) / 16, tail0 = head + n_vec * 16;
+	for (u32 i = tid; i < head; i += TR_THREADS)
+		dst[i] = img[i];
+	const TrVec16 *src16 = reinterpret_cast<const TrVec16 *>(img + head);
+	TrVec16 *dst16 = reinterpret_cast<TrVec16 *>(dst + head);
+	for (u32 i = tid; i < n_vec; i += TR_THREADS)
+		dst16[i] = src16[i];
+	for (u32 i = tail0 + tid; i < total; i += TR_THREADS)
+		dst[i] = img[i];
+}
+
 #endif

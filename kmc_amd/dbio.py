@@ -30,6 +30,8 @@ class Database:
     lut: np.ndarray = None   # KMC1: uint64[4^p], entry i = records with a prefix below i
     recs: np.ndarray = None  # KMC1: uint8, total_kmers records of (k - p) / 4 + counter_size bytes
     bins: list = field(default_factory=list)  # KMC2: per bin (record bytes, uint64[4^p] records per prefix)
+    raw_recs: np.ndarray = None  # KMC2: the body as it lies in the file (the bins' records one after the other), uint8
+    raw_lut: np.ndarray = None   # KMC2: the file's LUT, uint64[n_bins * 4^p + 1] global record offsets, the last one total_kmers (kmc2_db_reader.h:1731-1791)
 
     @property
     def rec_bytes(self) -> int:
@@ -82,6 +84,7 @@ def read_database(path: str) -> Database:
     n_bins = (lut_area.size - 1) // n_entries
     offs = np.concatenate([lut_area[: n_bins * n_entries], lut_area[-1:]])
     rb = db.rec_bytes
+    db.raw_recs, db.raw_lut = body[: total * rb].copy(), offs.copy()
     for b in range(n_bins):
         ob = offs[b * n_entries: (b + 1) * n_entries + 1].astype(np.int64)
         db.bins.append((body[ob[0] * rb: ob[-1] * rb].copy(), np.diff(ob).astype(np.uint64)))

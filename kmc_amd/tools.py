@@ -1,9 +1,12 @@
 """python -m kmc_amd.tools simple <db1> [-ci<v> -cx<v>] <db2> [-ci<v> -cx<v>] <operation> <out> [-ci<v> -cx<v> -cs<v> -oc<mode>] [<operation> <out> ...]
 python -m kmc_amd.tools filter [-t | -hm] <db> [-ci<v> -cx<v>] <reads> [-ci<v> -cx<v> -fa|-fq] <out> [-fa|-fq]
+python -m kmc_amd.tools transform <db> [-ci<v> -cx<v>] <oper> [-s] <out> [-ci<v> -cx<v> -cs<v> -okmc] [<oper> ...]
 
-`kmc_tools simple` and `kmc_tools filter` on the device: the argument order and the defaults are the reference's (kmc_tools/parameters_parser.cpp), the databases and
-the reads written are byte for byte those kmc_tools writes. simple: one kmc_hip_db_set_op_device call per output. filter: one kmc_hip_db_query_reads_device call per part
-of the reads file. A database as `kmc` wrote it (KMC2) is ordered on the device first."""
+`kmc_tools simple`, `kmc_tools filter` and `kmc_tools transform` on the device: the argument order and the defaults are the reference's (kmc_tools/parameters_parser.cpp),
+the databases, the reads and the text written are byte for byte those kmc_tools writes. simple: one kmc_hip_db_set_op_device call per output. filter: one
+kmc_hip_db_query_reads_device call per part of the reads file. transform: the input uploaded once, then per output kmc_hip_db_reduce_device (reduce, compact, set_counts,
+sort), kmc_hip_db_histogram_device, or kmc_hip_db_dump_device per part of the text. A database as `kmc` wrote it (KMC2) is ordered on the device first — by transform
+only when an output needs the order."""
 from __future__ import annotations
 
 import os
@@ -83,11 +86,17 @@ DEFAULT_COUNTER_OP = {"intersect": "min", "union": "sum"}  # config.h:96-110; ev
 class _DeviceDb:
     """an input's KMC1 body in HBM"""
 
-    def __init__(self, ctx, db: dbio.Database):
+    def __init__(self, ctx, db: dbio.Database, order: bool = True):
+        """order False: a KMC2 body stays as it lies in the file, under the file's LUT of n_seg x 4^p global offsets and the closing entry (what transform's
+        histogram and unordered dump read)"""
         self.ctx, self.db = ctx, db
         self.allocs = []
-        if db.kmc2:
+        self.n_seg = 1
+        if db.kmc2 and order:
             self._order(db)
+        elif db.kmc2:
+            self.p, self.n, self.n_seg = db.lut_prefix_len, db.total_kmers, (db.raw_lut.size - 1) >> (2 * db.lut_prefix_len)
+            self.d_recs, self.d_lut = self._up(db.raw_recs), self._up(db.raw_lut)
         else:
             self.p, self.n = db.lut_prefix_len, db.total_kmers
             self.d_recs, self.d_lut = self._up(db.recs), self._up(db.lut)
@@ -396,13 +405,222 @@ def filter_reads(argv, ctx=None) -> dict:
     return total
 
 
+TRANSFORM_USAGE = """usage: python -m kmc_amd.tools transform <db> [-ci<v> -cx<v>] <oper> [-s] <out> [-ci<v> -cx<v> -cs<v> -okmc] [<oper> ...]
+  <db>     -ci / -cx: k-mers with a counter outside [ci, cx] are absent for every output (default: the database's own cutoffs)
+  <oper>   sort | reduce | compact | set_counts <value>  write a KMC database <out> (-ci -cx: drop counters outside; -cs: clamp; compact stores counter 1)
+           histogram  writes `counter<TAB>k-mers` for every counter in [-ci, -cx] (default -cx: the smallest of the database's, 10000 and what its counter bytes hold)
+           dump [-s]  writes `k-mer<TAB>counter` per k-mer; -s, or any database output on the command line: in ascending k-mer order, otherwise in the input's order
+  any number of <oper> ... <out> groups; the input is read once"""
+TRANSFORM_DB_OPS = ("sort", "reduce", "compact", "set_counts")
+HISTOGRAM_MAX_COUNTER_DEFAULT = 10000  # kmc_tools/defs.h
+HISTOGRAM_MAX_BINS = 1 << 28
+U32_MAX = 0xFFFFFFFF
+
+
+def _num1(arg: str, name: str) -> int:
+    """parameters_parser.cpp:16-25 replace_zero: a value of 0 is taken as 1"""
+    return max(_num(arg, name), 1)
+
+
+def parse_transform(argv):
+    """-> ((path, ci, cx), [dict(op, path, sorted, ci, cx, cs, value)]); ci / cx / cs None = not given (parameters_parser.cpp:228-270,272-453)"""
+    if not argv or argv[0].startswith("-"):
+        raise UsageError("transform needs an input database\n" + TRANSFORM_USAGE)
+    path, ci, cx = argv[0], None, None
+    pos = 1
+    while pos < len(argv) and argv[pos].startswith("-"):
+        if argv[pos].startswith("-ci"):
+            ci = _num1(argv[pos], "-ci")
+        elif argv[pos].startswith("-cx"):
+            cx = _num1(argv[pos], "-cx")
+        else:
+            raise UsageError(f"unknown input option {argv[pos]}")
+        pos += 1
+    outputs = []
+    while pos < len(argv):
+        op = argv[pos]
+        if op not in TRANSFORM_DB_OPS + ("histogram", "dump"):
+            raise UsageError(f"unknown operation: {op} (one of sort, reduce, compact, histogram, dump, set_counts)")
+        o = dict(op=op, path=None, sorted=False, ci=None, cx=None, cs=None, value=0)
+        pos += 1
+        if op == "set_counts":
+            if pos >= len(argv):
+                raise UsageError("set_counts operation requires count value")
+            if not argv[pos].isdigit():
+                raise UsageError(f"Count value expected, but {argv[pos]} found")
+            o["value"] = int(argv[pos])
+            if o["value"] > U32_MAX:
+                raise UsageError(f"set_counts: counter values up to {U32_MAX} are supported")
+            pos += 1
+        while pos < len(argv) and argv[pos].startswith("-"):
+            if argv[pos] != "-s":
+                raise UsageError(f"unknown operation parameter: {argv[pos]}")
+            if op != "dump":
+                raise UsageError("-s parameter allowed only for dump operation")
+            o["sorted"] = True
+            pos += 1
+        if pos >= len(argv):
+            raise UsageError(f"Output path missed ({op})")
+        o["path"] = argv[pos]
+        pos += 1
+        while pos < len(argv) and argv[pos].startswith("-"):
+            a = argv[pos]
+            if a.startswith("-ci"):
+                o["ci"] = _num1(a, "-ci")
+            elif a.startswith("-cx"):
+                o["cx"] = _num1(a, "-cx")
+            elif a.startswith("-cs"):
+                o["cs"] = _num1(a, "-cs")
+            elif a.startswith("-o"):
+                if op not in TRANSFORM_DB_OPS:
+                    raise UsageError("-o parameter allowed only for compact, reduce, set_counts and sort operations")
+                if a[2:] != "kmc":
+                    raise UsageError(f"{a}: KFF output is not written, only KMC databases")
+            else:
+                raise UsageError(f"Unknown parameter: {a}")
+            pos += 1
+        outputs.append(o)
+    if not outputs:
+        raise UsageError("transform needs at least one <oper> <out>\n" + TRANSFORM_USAGE)
+    return (path, ci, cx), outputs
+
+
+def resolve_transform(outputs, db: dbio.Database, in_ci: int, in_cx: int) -> list:
+    """The defaults of parameters_parser.cpp:437-450,867-892 -> per output dict(op, path, ci, cx, cs, value, cs_bytes (database outputs))."""
+    full = (1 << (8 * db.counter_size)) - 1
+    res = []
+    for o in outputs:
+        r = dict(op=o["op"], path=o["path"], value=o["value"])
+        if o["op"] == "set_counts":  # the three options are ignored; a value of 0 sets nothing (kmc1_db_writer.h:378)
+            r.update(ci=1, cx=U32_MAX, cs=U32_MAX)
+        else:
+            r["ci"] = o["ci"] or in_ci
+            r["cx"] = o["cx"] or (min(db.max_count, HISTOGRAM_MAX_COUNTER_DEFAULT, full) if o["op"] == "histogram" else in_cx)
+            r["cs"] = 1 if o["op"] == "compact" else (o["cs"] or full)
+        if o["op"] in TRANSFORM_DB_OPS:
+            r["cs_bytes"] = dbio.byte_log(r["value"]) if r["value"] else min(dbio.byte_log(r["cs"]), dbio.byte_log(r["cx"]))  # kmc1_db_writer.h:154-156
+        res.append(r)
+    return res
+
+
+def _transform_database(ctx, dev, view, db, r) -> dict:
+    k = db.kmer_len
+    p_out = dbio.best_lut_prefix_len(k, db.total_kmers)  # kmc1_db_writer.h:425-456, over the input header's total
+    rb = (k - p_out) // 4 + r["cs_bytes"]
+    d_out, d_lut = ctx.malloc(dev.n * rb + 256), ctx.malloc(8 << (2 * p_out))
+    try:
+        n, st = ctx.db_reduce_device(k, view, r["ci"], r["cx"], min(r["cs"], U32_MAX), r["value"], p_out, d_out, dev.n * rb, d_lut)
+        recs, lut = np.zeros(n * rb, dtype=np.uint8), np.zeros(1 << (2 * p_out), dtype=np.uint64)
+        if n:
+            ctx.d2h(recs, d_out)
+        ctx.d2h(lut, d_lut)
+    finally:
+        ctx.free(d_out)
+        ctx.free(d_lut)
+    dbio.write_kmc1(r["path"], k, r["cs_bytes"], p_out, r["ci"], r["cx"], db.both_strands, lut, recs, mode=db.mode)
+    return st
+
+
+def _transform_histogram(ctx, dev, view, db, r) -> dict:
+    ci, cx = r["ci"], min(r["cx"], U32_MAX)
+    if cx < ci:  # histogram_writer.h:45: no line
+        open(r["path"], "wb").close()
+        return dict.fromkeys(capi.DBH_STATS, 0)
+    n_bins = cx - ci + 1
+    d_hist = ctx.malloc(8 * n_bins + 256)
+    try:
+        st = ctx.db_histogram_device(db.kmer_len, view, dev.n_seg, ci, cx, d_hist)
+        hist = np.zeros(n_bins, dtype=np.uint64)
+        ctx.d2h(hist, d_hist)
+    finally:
+        ctx.free(d_hist)
+    with open(r["path"], "wb") as f:  # histogram_writer.h:45-48
+        for i0 in range(0, n_bins, 1 << 16):
+            f.write("".join(f"{ci + i0 + i}\t{c}\n" for i, c in enumerate(hist[i0:i0 + (1 << 16)].tolist())).encode())
+    return st
+
+
+def _transform_dump(ctx, dev, view, db, r) -> dict:
+    k = db.kmer_len
+    part_bytes = max(1, int(float(os.environ.get("KMC_HIP_DUMP_PART_MB", "64")) * (1 << 20)))
+    part = max(1, part_bytes // (k + 12))  # records of a part: a record is at most k + 12 bytes of text
+    cap = min(part, max(dev.n, 1)) * (k + 12)
+    total = dict.fromkeys(capi.DBT_STATS, 0)
+    total["n_bytes"] = 0
+    d_text = ctx.malloc(cap + 256)
+    try:
+        with open(r["path"], "wb") as f:
+            for first in range(0, dev.n, part):
+                n_bytes, st = ctx.db_dump_device(k, view, dev.n_seg, first, min(part, dev.n - first), r["ci"], r["cx"], min(r["cs"], U32_MAX), d_text, cap)
+                if n_bytes:
+                    text = np.zeros(n_bytes, dtype=np.uint8)
+                    ctx.d2h(text, d_text)
+                    f.write(text.tobytes())
+                total["n_bytes"] += n_bytes
+                for key in capi.DBT_STATS:
+                    total[key] += st[key]
+    finally:
+        ctx.free(d_text)
+    return total
+
+
+def transform(argv, ctx=None) -> list:
+    """Runs the command line; returns per output that is written the dict of tallies of its device call(s) (a dump: summed over its parts, with n_bytes)."""
+    (path, ci, cx), outputs = parse_transform(argv)
+    if dbio.is_kff(path) and not os.path.exists(path + ".kmc_pre"):
+        raise UsageError(f"{path}: a KFF file; only KMC databases are read")
+    try:
+        db = dbio.read_database(path)
+    except (dbio.DbFormatError, OSError) as e:
+        raise UsageError(str(e))
+    if db.counter_size == 0:
+        raise UsageError(f"{path}: counter size 0 (a k-mer set without counters) is not supported, as in kmc_tools")
+    if not db.kmc2 and any(o["op"] == "sort" for o in outputs):  # kmc_tools.cpp:421-437
+        print("Warning: input database is already sorted. Each sort operation will be omitted", file=sys.stderr)
+        outputs = [o for o in outputs if o["op"] != "sort"]
+        if not outputs:
+            return []
+    in_ci, in_cx = ci or db.min_count, cx or db.max_count
+    res = resolve_transform(outputs, db, in_ci, in_cx)
+    for r in res:
+        if r["op"] == "histogram" and min(r["cx"], U32_MAX) - r["ci"] + 1 > HISTOGRAM_MAX_BINS:
+            raise UsageError(f"histogram {r['path']}: a range of {min(r['cx'], U32_MAX) - r['ci'] + 1} counters; at most 2^28 = {HISTOGRAM_MAX_BINS} are written (give -cx)")
+    # kmc_tools.cpp:440-465: one database output or one dump -s and every output sees the k-mers in ascending order
+    need_order = any(o["op"] in TRANSFORM_DB_OPS or o["sorted"] for o in outputs)
+    own = ctx is None
+    if own:
+        ctx = capi.Context((0,))
+    dev = None
+    results = []
+    try:
+        dev = _DeviceDb(ctx, db, order=need_order)
+        view = dev.view(max(in_ci, 0), in_cx)
+        for r in res:
+            run = _transform_histogram if r["op"] == "histogram" else _transform_dump if r["op"] == "dump" else _transform_database
+            results.append(run(ctx, dev, view, db, r))
+    finally:
+        if dev:
+            dev.free()
+        if own:
+            ctx.close()
+    return results
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if argv and argv[0] == "filter":
         print(", ".join(f"{a} {b}" for a, b in filter_reads(argv[1:]).items()))
         return 0
+    if argv and argv[0] == "transform":
+        outs = [o for o in parse_transform(argv[1:])[1]]
+        sts = transform(argv[1:])
+        if len(sts) != len(outs):  # an ordered input: the sorts were left out
+            outs = [o for o in outs if o["op"] != "sort"]
+        for (o, st) in zip(outs, sts):
+            print(f"{o['op']} -> {o['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
+        return 0
     if not argv or argv[0] != "simple":
-        raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...\n" + FILTER_USAGE)
+        raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...\n" + FILTER_USAGE + "\n" + TRANSFORM_USAGE)
     for (o, st) in zip(parse_simple(argv[1:])[1], simple(argv[1:])):
         print(f"{o['op']} -> {o['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
     return 0
