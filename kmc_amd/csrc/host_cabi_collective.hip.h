@@ -115,11 +115,10 @@ int kmc_hip_order_database_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_p
 		return fail(KMC_HIP_EINVAL, "kmc_hip_order_database_device: NULL argument");
 	if (P.kff || !P.lut_prefix_len || P.without_output)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_order_database_device: needs KMC-format bins (lut_prefix_len > 0, with output)");
-	if (out_lut_prefix_len < 1 || out_lut_prefix_len > 15 || out_lut_prefix_len >= P.k || (P.k - out_lut_prefix_len) % 4)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_order_database_device: (kmer_len - out_lut_prefix_len) must be a positive multiple of 4, out_lut_prefix_len 1..15");
-	const u32 words = (P.k + 31) / 32;
-	if (words + 1 > 8)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_order_database_device: kmer_len <= 224");
+	if (int rc = check_prefix_len("kmc_hip_order_database_device", "out_lut_prefix_len", out_lut_prefix_len, P.k))
+		return rc;
+	if (int rc = check_unpacked_width("kmc_hip_order_database_device", P.k))
+		return rc;
 	/* the bins may come from asynchronous kmc_hip_process_bins_device calls on any stream slot: wait for all of them, run the groups whose hybrid sort asked
 	 * for LSD passes again, raise their deferred errors (the body of kmc_hip_synchronize) — before a single out_bytes is read */
 	if (int rc = kmc_hip_synchronize(ctx, dev))
@@ -141,25 +140,12 @@ int kmc_hip_order_database_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_p
 	if (n_total * rb_out > out_capacity)
 		return fail(KMC_HIP_ECAPACITY, "kmc_hip_order_database_device: out_capacity too small");
 	s.timed = false;
-	int rc = KMC_HIP_EINVAL;
-	switch (words) {
-	case 1: rc = order_database_t<1>(s, P, bins, n_of, n_total, out_lut_prefix_len, d_out, (u64 *)d_lut_out); break;
-	case 2: rc = order_database_t<2>(s, P, bins, n_of, n_total, out_lut_prefix_len, d_out, (u64 *)d_lut_out); break;
-	case 3: rc = order_database_t<3>(s, P, bins, n_of, n_total, out_lut_prefix_len, d_out, (u64 *)d_lut_out); break;
-	case 4: rc = order_database_t<4>(s, P, bins, n_of, n_total, out_lut_prefix_len, d_out, (u64 *)d_lut_out); break;
-	case 5: rc = order_database_t<5>(s, P, bins, n_of, n_total, out_lut_prefix_len, d_out, (u64 *)d_lut_out); break;
-	case 6: rc = order_database_t<6>(s, P, bins, n_of, n_total, out_lut_prefix_len, d_out, (u64 *)d_lut_out); break;
-	case 7: rc = order_database_t<7>(s, P, bins, n_of, n_total, out_lut_prefix_len, d_out, (u64 *)d_lut_out); break;
-	}
-	if (rc)
+	if (int rc = by_words<7>((P.k + 31) / 32, [&](auto W) { return order_database_t<decltype(W)::value>(s, P, bins, n_of, n_total, out_lut_prefix_len, d_out, (u64 *)d_lut_out); }))
 		return rc;
 	HIPCHK(hipStreamSynchronize(s.stream));
-	if (int rc2 = harvest(s))
-		return rc2;
-	u32 err = 0;
-	if (int rc2 = read_and_clear_sticky(s, err))
-		return rc2;
-	return err_to_code(err);
+	if (int rc = harvest(s))
+		return rc;
+	return finish(s);
 }
 
 int kmc_hip_set_hybrid(int mode)

@@ -24,23 +24,10 @@ int kmc_hip_debug_expand(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_params *pa
 	HIPCHK(hipMemset((char *)s.in.p + size, 0, 256));
 	HIPCHK(hipMemcpy(s.pack_start.p, ps.data(), ps.size() * 8, hipMemcpyHostToDevice));
 	const u32 words = (P.k + 31) / 32;
-	switch (words) {
-	case 1: rc = debug_expand_t<1>(s, P, size, n_rec, n_packs); break;
-	case 2: rc = debug_expand_t<2>(s, P, size, n_rec, n_packs); break;
-	case 3: rc = debug_expand_t<3>(s, P, size, n_rec, n_packs); break;
-	case 4: rc = debug_expand_t<4>(s, P, size, n_rec, n_packs); break;
-	case 5: rc = debug_expand_t<5>(s, P, size, n_rec, n_packs); break;
-	case 6: rc = debug_expand_t<6>(s, P, size, n_rec, n_packs); break;
-	case 7: rc = debug_expand_t<7>(s, P, size, n_rec, n_packs); break;
-	default: rc = debug_expand_t<8>(s, P, size, n_rec, n_packs); break;
-	}
-	if (rc)
+	if ((rc = by_words<8>(words, [&](auto W) { return debug_expand_t<decltype(W)::value>(s, P, size, n_rec, n_packs); })))
 		return rc;
 	HIPCHK(hipStreamSynchronize(s.stream));
-	u32 err = 0;
-	if ((rc = read_and_clear_sticky(s, err)))
-		return rc;
-	if ((rc = err_to_code(err)))
+	if ((rc = finish(s)))
 		return rc;
 	HIPCHK(hipMemcpy(out_recs, s.recA.p, n_rec * words * 8, hipMemcpyDeviceToHost));
 	return 0;
@@ -64,25 +51,12 @@ int kmc_hip_debug_compact(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_params *p
 	if ((rc = ensure(s.recA, n * words * 8 + 256)) || (rc = ensure(s.out, out_capacity + 256)) || (rc = ensure(s.lut, lut_entries * 8 + 256)))
 		return rc;
 	HIPCHK(hipMemcpy(s.recA.p, sorted_recs, n * words * 8, hipMemcpyHostToDevice));
-	switch (words) {
-	case 1: rc = debug_compact_t<1>(s, P, n, out_capacity, lut_entries); break;
-	case 2: rc = debug_compact_t<2>(s, P, n, out_capacity, lut_entries); break;
-	case 3: rc = debug_compact_t<3>(s, P, n, out_capacity, lut_entries); break;
-	case 4: rc = debug_compact_t<4>(s, P, n, out_capacity, lut_entries); break;
-	case 5: rc = debug_compact_t<5>(s, P, n, out_capacity, lut_entries); break;
-	case 6: rc = debug_compact_t<6>(s, P, n, out_capacity, lut_entries); break;
-	case 7: rc = debug_compact_t<7>(s, P, n, out_capacity, lut_entries); break;
-	default: rc = debug_compact_t<8>(s, P, n, out_capacity, lut_entries); break;
-	}
-	if (rc)
+	if ((rc = by_words<8>(words, [&](auto W) { return debug_compact_t<decltype(W)::value>(s, P, n, out_capacity, lut_entries); })))
 		return rc;
 	HIPCHK(hipStreamSynchronize(s.stream));
 	HostRes r;
 	HIPCHK(hipMemcpy(&r, s.zero.p, sizeof r, hipMemcpyDeviceToHost));
-	u32 err = 0;
-	if ((rc = read_and_clear_sticky(s, err)))
-		return rc;
-	if ((rc = err_to_code(err)))
+	if ((rc = finish(s)))
 		return rc;
 	if (r.out_bytes > out_capacity)
 		return fail(KMC_HIP_ECAPACITY, "out_capacity too small");
@@ -117,53 +91,33 @@ int kmc_hip_debug_split_reads(kmc_hip_ctx *ctx, int dev, const int8_t *codes, ui
 	if (tiles > 0x7FFFFFFFull)
 		return fail(KMC_HIP_EINVAL, "too many symbols for one call");
 	void *d_codes = nullptr, *d_sig = nullptr, *d_status = nullptr, *d_pos = nullptr, *d_len = nullptr, *d_ssig = nullptr, *d_small = nullptr;
-	auto release = [&] {
-		for (void *p : {d_codes, d_sig, d_status, d_pos, d_len, d_ssig, d_small})
-			if (p)
-				(void)hipFree(p);
-	};
-#define S1CHK(call)                                                                                                    \
-	do {                                                                                                               \
-		hipError_t e__ = (call);                                                                                       \
-		if (e__ != hipSuccess) {                                                                                       \
-			release();                                                                                                 \
-			return fail_hip(#call, e__);                                                                               \
-		}                                                                                                              \
-	} while (0)
+	DevTemps tmp;
+	int rc = 0;
 	const u64 cap = sk_cap ? sk_cap : 1;
-	S1CHK(hipMalloc(&d_codes, n));
-	S1CHK(hipMalloc(&d_sig, n * 4));
 	const u64 ctiles = s1_cut_tiles(n); /* the cutting kernel works on S1_SUB tiles per workgroup */
-	S1CHK(hipMalloc(&d_status, ctiles * 16));
-	S1CHK(hipMalloc(&d_pos, cap * 8));
-	S1CHK(hipMalloc(&d_len, cap * 4));
-	S1CHK(hipMalloc(&d_ssig, cap * 4));
-	S1CHK(hipMalloc(&d_small, 64));
-	S1CHK(hipMemcpyAsync(d_codes, codes, n, hipMemcpyHostToDevice, s.stream));
-	S1CHK(hipMemsetAsync(d_status, 0, ctiles * 16, s.stream));
-	S1CHK(hipMemsetAsync(d_small, 0, 64, s.stream));
+	if ((rc = tmp.alloc(&d_codes, n)) || (rc = tmp.alloc(&d_sig, n * 4)) || (rc = tmp.alloc(&d_status, ctiles * 16)) || (rc = tmp.alloc(&d_pos, cap * 8)) ||
+	    (rc = tmp.alloc(&d_len, cap * 4)) || (rc = tmp.alloc(&d_ssig, cap * 4)) || (rc = tmp.alloc(&d_small, 64)))
+		return rc;
+	HIPCHK(hipMemcpyAsync(d_codes, codes, n, hipMemcpyHostToDevice, s.stream));
+	HIPCHK(hipMemsetAsync(d_status, 0, ctiles * 16, s.stream));
+	HIPCHK(hipMemsetAsync(d_small, 0, 64, s.stream));
 	k_s1_signatures<<<dim3((u32)tiles), dim3(S1_BLOCK), 0, s.stream>>>((const int8_t *)d_codes, n, kmer_len, signature_len, (u32 *)d_sig);
 	k_s1_cut<false><<<dim3((u32)ctiles), dim3(S1_BLOCK), 0, s.stream>>>((const u32 *)d_sig, (const int8_t *)nullptr, 0u, n, kmer_len,
 	                                                                      (u64 *)d_status, (u64 *)d_status + ctiles, (u32 *)d_small + 2, (u64 *)d_pos, (u32 *)d_len,
 	                                                                     (u32 *)d_ssig, sk_cap, (u64 *)d_small, (const u64 *)nullptr, err_ptr(s));
-	S1CHK(hipGetLastError());
+	HIPCHK(hipGetLastError());
 	u64 cnt = 0;
-	S1CHK(hipMemcpyAsync(&cnt, d_small, 8, hipMemcpyDeviceToHost, s.stream));
-	S1CHK(hipMemcpyAsync(sig, d_sig, n * 4, hipMemcpyDeviceToHost, s.stream));
-	S1CHK(hipStreamSynchronize(s.stream));
+	HIPCHK(hipMemcpyAsync(&cnt, d_small, 8, hipMemcpyDeviceToHost, s.stream));
+	HIPCHK(hipMemcpyAsync(sig, d_sig, n * 4, hipMemcpyDeviceToHost, s.stream));
+	HIPCHK(hipStreamSynchronize(s.stream));
 	const u64 take = cnt < sk_cap ? cnt : sk_cap;
 	if (take) {
-		S1CHK(hipMemcpy(sk_pos, d_pos, take * 8, hipMemcpyDeviceToHost));
-		S1CHK(hipMemcpy(sk_len, d_len, take * 4, hipMemcpyDeviceToHost));
-		S1CHK(hipMemcpy(sk_sig, d_ssig, take * 4, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(sk_pos, d_pos, take * 8, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(sk_len, d_len, take * 4, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(sk_sig, d_ssig, take * 4, hipMemcpyDeviceToHost));
 	}
-#undef S1CHK
-	release();
 	*n_sk = cnt;
-	u32 err = 0;
-	if (int rc = read_and_clear_sticky(s, err))
-		return rc;
-	return err_to_code(err);
+	return finish(s);
 }
 
 /* ---- stage 1 on the device: reads -> bins in HBM, ready for kmc_hip_process_bins_device ---- */
@@ -203,49 +157,34 @@ int kmc_hip_split_reads_plan(kmc_hip_ctx *ctx, int dev, const int8_t *d_codes, u
 	*plan = nullptr;
 	Slot &s = ctx->devs[dev]->slot[0];
 	std::lock_guard<std::mutex> lck(s.mtx);
-	kmc_hip_s1_plan *p = new kmc_hip_s1_plan;
+	std::unique_ptr<kmc_hip_s1_plan, void (*)(kmc_hip_s1_plan *)> p(new kmc_hip_s1_plan, s1_plan_release); /* ours until it is handed to the caller */
 	p->dev = dev, p->k = kmer_len, p->n_bins = n_bins, p->n = n, p->d_codes = d_codes, p->d_map = d_sig_to_bin;
 	void *d_status = nullptr, *d_small = nullptr;
-	auto release_tmp = [&] {
-		for (void *q : {d_status, d_small})
-			if (q)
-				(void)hipFree(q);
-	};
-#define S1CHK(call)                                                                                                    \
-	do {                                                                                                               \
-		hipError_t e__ = (call);                                                                                       \
-		if (e__ != hipSuccess) {                                                                                       \
-			release_tmp();                                                                                             \
-			s1_plan_release(p);                                                                                        \
-			return fail_hip(#call, e__);                                                                               \
-		}                                                                                                              \
-	} while (0)
-	S1CHK(hipMalloc(&d_status, tiles * 16));
-	S1CHK(hipMalloc(&d_small, 64));
-	S1CHK(hipMalloc(&p->d_tot, (size_t)3 * n_bins * 8));
-	S1CHK(hipMalloc(&p->d_lay, (size_t)(3 * n_bins + 2) * 8));
+	DevTemps tmp;
+	int rc = 0;
+	if ((rc = tmp.alloc(&d_status, tiles * 16)) || (rc = tmp.alloc(&d_small, 64)))
+		return rc;
+	HIPCHK(hipMalloc(&p->d_tot, (size_t)3 * n_bins * 8));
+	HIPCHK(hipMalloc(&p->d_lay, (size_t)(3 * n_bins + 2) * 8));
 	/* signatures are computed inside the cutting kernel (never stored). The number of super-k-mers is only known after the cut: a first guess (one per 8 symbols; real reads give one per 10-40 at k = 27), and a
 	 * second cut with the exact number when the guess was short */
 	u64 cap = n / 8 + 4096, cnt = 0;
 	for (int attempt = 0; attempt < 2; ++attempt) {
-		S1CHK(hipMalloc(&p->d_pos, cap * 8));
-		S1CHK(hipMalloc(&p->d_len, cap * 4));
-		S1CHK(hipMalloc(&p->d_ssig, cap * 4));
-		S1CHK(hipMemsetAsync(d_status, 0, tiles * 16, s.stream));
-		S1CHK(hipMemsetAsync(d_small, 0, 64, s.stream));
+		HIPCHK(hipMalloc(&p->d_pos, cap * 8));
+		HIPCHK(hipMalloc(&p->d_len, cap * 4));
+		HIPCHK(hipMalloc(&p->d_ssig, cap * 4));
+		HIPCHK(hipMemsetAsync(d_status, 0, tiles * 16, s.stream));
+		HIPCHK(hipMemsetAsync(d_small, 0, 64, s.stream));
 		k_s1_cut<true><<<dim3((u32)tiles), dim3(S1_BLOCK), 0, s.stream>>>((const u32 *)nullptr, d_codes, signature_len, n, kmer_len, (u64 *)d_status,
 		                                                                    (u64 *)d_status + tiles, (u32 *)d_small + 2, (u64 *)p->d_pos, (u32 *)p->d_len,
 		                                                                    (u32 *)p->d_ssig, cap, (u64 *)d_small, (const u64 *)nullptr, (u32 *)d_small + 4);
-		S1CHK(hipGetLastError());
+		HIPCHK(hipGetLastError());
 		u64 small[3] = {0, 0, 0}; /* count | ticket | the cut's own error word: a short guess must not poison the stream's sticky word */
-		S1CHK(hipMemcpyAsync(small, d_small, sizeof small, hipMemcpyDeviceToHost, s.stream));
-		S1CHK(hipStreamSynchronize(s.stream));
+		HIPCHK(hipMemcpyAsync(small, d_small, sizeof small, hipMemcpyDeviceToHost, s.stream));
+		HIPCHK(hipStreamSynchronize(s.stream));
 		cnt = small[0];
-		if ((u32)small[2] & ~KERR_CAPACITY) {
-			release_tmp();
-			s1_plan_release(p);
+		if ((u32)small[2] & ~KERR_CAPACITY)
 			return err_to_code((u32)small[2] & ~KERR_CAPACITY);
-		}
 		if (cnt <= cap)
 			break;
 		for (void **q : {&p->d_pos, &p->d_len, &p->d_ssig}) {
@@ -255,32 +194,23 @@ int kmc_hip_split_reads_plan(kmc_hip_ctx *ctx, int dev, const int8_t *d_codes, u
 		cap = cnt;
 	}
 	p->n_sk = cnt;
-	S1CHK(hipMemsetAsync(p->d_tot, 0, (size_t)3 * n_bins * 8, s.stream));
+	HIPCHK(hipMemsetAsync(p->d_tot, 0, (size_t)3 * n_bins * 8, s.stream));
 	u64 *tot = (u64 *)p->d_tot, *lay = (u64 *)p->d_lay;
 	const u32 sk_tiles = (u32)((cnt + S1_SK_TILE - 1) / S1_SK_TILE);
 	if (sk_tiles)
 		k_s1_bin_totals<<<dim3(sk_tiles), dim3(256), 0, s.stream>>>((const u32 *)p->d_len, (const u32 *)p->d_ssig, cnt, kmer_len, d_sig_to_bin, n_bins, tot, tot + n_bins,
 		                                                             tot + 2 * n_bins, err_ptr(s));
 	k_s1_bin_layout<<<dim3(1), dim3(256), 0, s.stream>>>(tot, n_bins, lay, lay + n_bins + 1, lay + 2 * n_bins + 2, (u64 *)nullptr);
-	S1CHK(hipGetLastError());
-	S1CHK(hipMemcpyAsync(bin_bytes, tot, (size_t)n_bins * 8, hipMemcpyDeviceToHost, s.stream));
-	S1CHK(hipMemcpyAsync(bin_superkmers, tot + n_bins, (size_t)n_bins * 8, hipMemcpyDeviceToHost, s.stream));
-	S1CHK(hipMemcpyAsync(bin_kmers, tot + 2 * n_bins, (size_t)n_bins * 8, hipMemcpyDeviceToHost, s.stream));
-	S1CHK(hipMemcpyAsync(bin_base, lay, (size_t)(n_bins + 1) * 8, hipMemcpyDeviceToHost, s.stream));
-	S1CHK(hipMemcpyAsync(pack_base, lay + n_bins + 1, (size_t)(n_bins + 1) * 8, hipMemcpyDeviceToHost, s.stream));
-	S1CHK(hipStreamSynchronize(s.stream));
-#undef S1CHK
-	release_tmp();
-	u32 err = 0;
-	if (int rc = read_and_clear_sticky(s, err)) {
-		s1_plan_release(p);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(bin_bytes, tot, (size_t)n_bins * 8, hipMemcpyDeviceToHost, s.stream));
+	HIPCHK(hipMemcpyAsync(bin_superkmers, tot + n_bins, (size_t)n_bins * 8, hipMemcpyDeviceToHost, s.stream));
+	HIPCHK(hipMemcpyAsync(bin_kmers, tot + 2 * n_bins, (size_t)n_bins * 8, hipMemcpyDeviceToHost, s.stream));
+	HIPCHK(hipMemcpyAsync(bin_base, lay, (size_t)(n_bins + 1) * 8, hipMemcpyDeviceToHost, s.stream));
+	HIPCHK(hipMemcpyAsync(pack_base, lay + n_bins + 1, (size_t)(n_bins + 1) * 8, hipMemcpyDeviceToHost, s.stream));
+	HIPCHK(hipStreamSynchronize(s.stream));
+	if ((rc = finish(s)))
 		return rc;
-	}
-	if (err) {
-		s1_plan_release(p);
-		return err_to_code(err);
-	}
-	*plan = p;
+	*plan = p.release();
 	return 0;
 }
 
@@ -359,34 +289,7 @@ int kmc_hip_estimate_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t
 		return rc;
 	if (kmer_len < 1 || kmer_len > (uint32_t)S1_MAX_K || s < 1 || s > 16 || r < 8 || r > 27)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_estimate_open: kmer_len 1..256, s 1..16, r 8..27");
-	Dev &d = *ctx->devs[dev];
-	std::lock_guard<std::mutex> lck(d.est_mtx);
-	if (d.d_est) {
-		if (d.est_k == kmer_len && d.est_s == s && d.est_r == r)
-			return 0;
-		return fail(KMC_HIP_EINVAL, "kmc_hip_estimate_open: an estimator with other parameters is open on this device");
-	}
-	const size_t bytes = ((size_t)2 << r) * sizeof(u32);
-	u32 *p = nullptr;
-	HIPCHK(hipMalloc((void **)&p, bytes));
-	hipError_t e = hipMemset(p, 0, bytes);
-	if (e == hipSuccess)
-		e = hipDeviceSynchronize();
-	if (e != hipSuccess) {
-		(void)hipFree(p);
-		return fail_hip("hipMemset(estimator counters)", e);
-	}
-	d.d_est = p;
-	d.est_k = kmer_len, d.est_s = s, d.est_r = r;
-	return 0;
-}
-
-static int estimate_wait_slots(Dev &d) /* what the device's slots have launched adds to the counters */
-{
-	for (auto &sl : d.slot)
-		if (sl.stream)
-			HIPCHK(hipStreamSynchronize(sl.stream));
-	return 0;
+	return accum_open(ctx->devs[dev]->est, "kmc_hip_estimate_open", "an estimator", kmer_len, s, r, (u64)2 << r, sizeof(u32));
 }
 
 int kmc_hip_estimate_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint32_t *dst)
@@ -394,17 +297,7 @@ int kmc_hip_estimate_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t co
 	if (int rc = set_dev(ctx, dev))
 		return rc;
 	Dev &d = *ctx->devs[dev];
-	std::lock_guard<std::mutex> lck(d.est_mtx);
-	if (!d.d_est)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_estimate_read: no estimator is open on this device");
-	const uint64_t entries = (uint64_t)2 << d.est_r;
-	if ((count && !dst) || first > entries || count > entries - first)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_estimate_read: [first, first + count) lies outside the 2^(r+1) entries");
-	if (int rc = estimate_wait_slots(d))
-		return rc;
-	if (count)
-		HIPCHK(hipMemcpy(dst, d.d_est + first, (size_t)count * sizeof(u32), hipMemcpyDeviceToHost));
-	return 0;
+	return accum_read(d.est, d, "kmc_hip_estimate_read", "estimator", first, count, dst, sizeof(u32));
 }
 
 int kmc_hip_estimate_close(kmc_hip_ctx *ctx, int dev)
@@ -412,67 +305,116 @@ int kmc_hip_estimate_close(kmc_hip_ctx *ctx, int dev)
 	if (int rc = set_dev(ctx, dev))
 		return rc;
 	Dev &d = *ctx->devs[dev];
-	std::unique_lock<std::mutex> lck(d.est_mtx);
-	/* a split call holds d_est from its check of the flag to its return, without the mutex: the counters outlive every such call */
-	d.est_idle.wait(lck, [&d] { return d.est_users == 0; });
-	if (!d.d_est)
-		return 0;
-	if (int rc = estimate_wait_slots(d))
-		return rc;
-	HIPCHK(hipFree(d.d_est));
-	d.d_est = nullptr;
-	d.est_k = d.est_s = d.est_r = 0;
+	return accum_close(d.est, d);
+}
+
+/* ---- what kmc_hip_split_part and kmc_hip_smallk_part share: the refusals that are not an entry's own, the call past them, the chain's return code ---- */
+namespace {
+int s1_part_check(const char *who, const kmc_hip_split_params *p, u64 size)
+{
+	const std::string w(who);
+	if (p->file_type > 4 || p->file_type == 3 || p->part_kind > 1)
+		return fail(KMC_HIP_EINVAL, w + ": unsupported parameters (file_type 0, 1, 2 or 4, part_kind 0 or 1)");
+	if ((p->file_type == 2 || p->file_type == 4) && p->part_kind != 0)
+		return fail(KMC_HIP_EINVAL, w + ": a part of multi-line FASTA (file_type 2) or of BAM records (file_type 4) is a ReadType::na part: part_kind must be 0");
+	if (p->file_type == 4 && size >= S1_BAM_MAX_PART)
+		return fail(KMC_HIP_EINVAL, w + ": a part of BAM records (file_type 4) must be smaller than 2 GiB");
+	/* a configuration limit, not a property of the text (ADVICE r5): the pieces of an over-long line are cut at workgroup windows (stage1_chain.h) */
+	if (p->line_cap < (uint64_t)p->kmer_len + S1_WG_TILE + 2)
+		return fail(KMC_HIP_EINVAL, w + ": line_cap (mem_part_pmm_reads) is too small for the device splitter: it needs kmer_len + " + std::to_string(S1_WG_TILE + 2) + " symbols at least");
 	return 0;
 }
+
+/* One part call past its refusals; the caller holds the slot's mutex. begin: the work area (per_byte: the entry's bytes of arena per byte of text, + 32 MiB), the
+ * backend on the slot's stream, the chain's parameters that do not belong to the bin path alone, the title taken off a long-read part. upload: the text on the device
+ * (throws S1BackendFailure like the backend). code: the chain's return code as the entry's, 0 = go on. */
+struct S1Part {
+	S1HipBackend be;
+	S1PartParams sp;
+	const uint8_t *text = nullptr;
+	u64 size = 0, long_reads = 0;
+	bool long_read = false;
+
+	int begin(Dev &d, int slot, const kmc_hip_split_params *p, const uint8_t *text_, u64 size_, size_t per_byte)
+	{
+		if (int rc = ensure(d.s1_arena[slot], (size_t)size_ * per_byte + ((size_t)32 << 20)))
+			return rc;
+		be.stream = d.slot[slot].stream;
+		be.slot = &d.slot[slot];
+		be.arena = &d.s1_arena[slot];
+		sp.k = p->kmer_len;
+		sp.m = 0, sp.n_bins = 0, sp.max_x = 0; /* the bin path's, like d_sig_to_bin: not read by the front half */
+		sp.both_strands = p->both_strands ? 1u : 0u;
+		sp.lines_per_record = p->file_type == 1 ? 4u : 2u;
+		sp.multiline_fasta = p->file_type == 2;
+		sp.bam = p->file_type == 4;
+		sp.homopolymer = (p->flags & KMC_HIP_SPLIT_HOMOPOLYMER) != 0;
+		sp.line_cap = p->line_cap;
+		sp.d_sig_to_bin = nullptr;
+		text = text_, size = size_;
+		long_read = p->part_kind == 1;
+		if (long_read) { /* the title (if the part has it) is taken off here, the symbols go up from an aligned buffer */
+			const u64 skip = s1_long_read_title(text, size, p->file_type, long_reads);
+			text += skip;
+			size -= skip;
+			sp.lines_per_record = 0;
+		}
+		return 0;
+	}
+	uint8_t *upload()
+	{
+		uint8_t *d_text = (uint8_t *)be.alloc(size + 16);
+		if (size) {
+			hipError_t e = hipMemcpyAsync(d_text, text, size, hipMemcpyHostToDevice, be.stream);
+			if (e != hipSuccess)
+				throw S1BackendFailure{e, "hipMemcpyAsync(text)"};
+		}
+		return d_text;
+	}
+	bool ends_with_newline() const { return size && text[size - 1] == '\n'; }
+	int code(const char *who, int chain_rc, S1PartResult &R) const
+	{
+		if (long_read)
+			R.n_reads = long_reads;
+		if (chain_rc == S1_CHAIN_UNCOVERED)
+			return KMC_HIP_UNCOVERED;
+		if (chain_rc != S1_CHAIN_OK)
+			return R.device_error ? err_to_code(R.device_error) : fail(KMC_HIP_EDEVICE, std::string(who) + ": stage-1 chain failed");
+		return 0;
+	}
+};
+} // namespace
 
 int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint8_t *recs,
                        uint64_t recs_capacity, uint64_t *recs_bytes, uint64_t *bin_off, uint64_t *bin_bytes, uint64_t *bin_kmers, uint64_t *bin_superkmers, uint64_t *bin_plus_x,
                        uint64_t *n_reads)
 {
+	const char *who = "kmc_hip_split_part";
 	if (int rc = set_dev(ctx, dev))
 		return rc;
 	if (!p || (size && !text) || !recs || !recs_bytes || !bin_off || !bin_bytes || !bin_kmers || !bin_superkmers || !bin_plus_x || !n_reads || slot < 0 || slot >= N_SLOTS)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: bad argument");
 	if (p->kmer_len < 1 || p->kmer_len > (uint32_t)S1_MAX_K || p->signature_len < 5 || p->signature_len > 11 || p->signature_len > p->kmer_len || p->n_bins < 1 ||
-	    p->n_bins > (uint32_t)S1_MAX_BINS || p->max_x > 3 || p->file_type > 4 || p->file_type == 3 || p->part_kind > 1 || (p->max_x && p->kmer_len < 4))
+	    p->n_bins > (uint32_t)S1_MAX_BINS || p->max_x > 3 || (p->max_x && p->kmer_len < 4))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: unsupported parameters");
 	if (p->flags & ~(KMC_HIP_SPLIT_HOMOPOLYMER | KMC_HIP_SPLIT_ESTIMATE))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: unknown bit in flags");
-	if (p->file_type == 2 && p->part_kind != 0)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: a multi-line FASTA part (file_type 2) is a ReadType::na part: part_kind must be 0");
-	if (p->file_type == 4 && p->part_kind != 0)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: a part of BAM records (file_type 4) is a ReadType::na part: part_kind must be 0");
-	if (p->file_type == 4 && size >= S1_BAM_MAX_PART)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: a part of BAM records (file_type 4) must be smaller than 2 GiB");
-	/* a configuration limit, not a property of the text (ADVICE r5): the pieces of an over-long line are cut at workgroup windows (stage1_chain.h) */
-	if (p->line_cap < (uint64_t)p->kmer_len + S1_WG_TILE + 2)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: line_cap (mem_part_pmm_reads) is too small for the device splitter: it needs kmer_len + " + std::to_string(S1_WG_TILE + 2) +
-		                                " symbols at least");
+	if (int rc = s1_part_check(who, p, size))
+		return rc;
 	Dev &d = *ctx->devs[dev];
 	if (!d.d_sig_map || d.sig_map_entries != (1u << (2 * p->signature_len)) + 1)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: kmc_hip_split_set_map was not called for this signature length");
 	u32 *d_est = nullptr;
 	u32 est_s = 0, est_r = 0;
-	struct EstUser { /* counted from here to the call's return, so that a concurrent kmc_hip_estimate_close cannot free d_est in front of the kernel */
-		Dev *d = nullptr;
-		~EstUser()
-		{
-			if (!d)
-				return;
-			std::lock_guard<std::mutex> lck(d->est_mtx);
-			if (--d->est_users == 0)
-				d->est_idle.notify_all();
-		}
-	} est_user;
+	AccumHold est_hold;
 	if (p->flags & KMC_HIP_SPLIT_ESTIMATE) {
-		std::lock_guard<std::mutex> lck(d.est_mtx);
-		if (!d.d_est)
+		std::lock_guard<std::mutex> lck(d.est.mtx);
+		if (!d.est.p)
 			return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: KMC_HIP_SPLIT_ESTIMATE without kmc_hip_estimate_open on this device");
-		if (d.est_k != p->kmer_len)
+		if (d.est.par[0] != p->kmer_len)
 			return fail(KMC_HIP_EINVAL, "kmc_hip_split_part: KMC_HIP_SPLIT_ESTIMATE: the open estimator has another kmer_len");
-		d_est = d.d_est, est_s = d.est_s, est_r = d.est_r;
-		++d.est_users;
-		est_user.d = &d;
+		d_est = (u32 *)d.est.p, est_s = d.est.par[1], est_r = d.est.par[2];
+		est_hold.take(d.est);
 	}
 	*recs_bytes = 0;
 	Slot &s = d.slot[slot];
@@ -483,47 +425,21 @@ int kmc_hip_split_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_
 	const bool hc = (p->flags & KMC_HIP_SPLIT_HOMOPOLYMER) != 0;
 	/* BAM records: two bases per byte, so codes, super-k-mers and records double; + 4 B per 36 B of text for the record offsets */
 	const size_t per_byte = p->file_type == 4 ? 14 + (hc ? 4 : 0) : (p->file_type == 2 ? 10 : 8) + (hc ? 2 : 0);
-	if (int rc = ensure(d.s1_arena[slot], (size_t)size * per_byte + ((size_t)32 << 20)))
+	S1Part part;
+	if (int rc = part.begin(d, slot, p, text, size, per_byte))
 		return rc;
-	S1HipBackend be;
-	be.stream = s.stream;
-	be.slot = &s;
-	be.arena = &d.s1_arena[slot];
-	S1PartParams sp;
-	sp.k = p->kmer_len;
+	S1PartParams &sp = part.sp;
 	sp.m = p->signature_len;
 	sp.n_bins = p->n_bins;
 	sp.max_x = p->max_x;
-	sp.both_strands = p->both_strands ? 1u : 0u;
-	sp.lines_per_record = p->file_type == 1 ? 4u : 2u;
-	sp.multiline_fasta = p->file_type == 2;
-	sp.bam = p->file_type == 4;
-	sp.homopolymer = hc;
-	sp.line_cap = p->line_cap;
 	sp.d_sig_to_bin = d.d_sig_map;
 	sp.sorted_emit = getenv("KMC_HIP_S1_SORTED_EMIT") != nullptr; /* the alternative emit (stage1_kernels.hip.h): to be measured before it becomes the default */
+	S1HipBackend &be = part.be;
 	S1PartResult R;
-	u64 long_reads = 0;
-	if (p->part_kind == 1) { /* a long-read part: the title (if the part has it) is taken off here, the symbols go up from an aligned buffer */
-		const u64 skip = s1_long_read_title(text, size, p->file_type, long_reads);
-		text += skip;
-		size -= skip;
-		sp.lines_per_record = 0;
-	}
 	try {
-		uint8_t *d_text = (uint8_t *)be.alloc(size + 16);
-		if (size) {
-			hipError_t e = hipMemcpyAsync(d_text, text, size, hipMemcpyHostToDevice, s.stream);
-			if (e != hipSuccess)
-				return fail_hip("hipMemcpyAsync(text)", e);
-		}
-		const int rc = s1_split_part(be, d_text, size, size && text[size - 1] == '\n', sp, R);
-		if (p->part_kind == 1)
-			R.n_reads = long_reads;
-		if (rc == S1_CHAIN_UNCOVERED)
-			return KMC_HIP_UNCOVERED;
-		if (rc != S1_CHAIN_OK)
-			return R.device_error ? err_to_code(R.device_error) : fail(KMC_HIP_EDEVICE, "kmc_hip_split_part: stage-1 chain failed");
+		uint8_t *d_text = part.upload();
+		if (int rc = part.code(who, s1_split_part(be, d_text, part.size, part.ends_with_newline(), sp, R), R))
+			return rc;
 		*recs_bytes = R.recs_bytes;
 		if (R.recs_bytes > recs_capacity)
 			return fail(KMC_HIP_ECAPACITY, "kmc_hip_split_part: recs_capacity too small, *recs_bytes holds what this part needs");
@@ -561,26 +477,7 @@ int kmc_hip_smallk_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t b
 		return rc;
 	if (kmer_len < 1 || kmer_len > S1_SMALLK_MAX_K)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_open: kmer_len 1..13");
-	Dev &d = *ctx->devs[dev];
-	std::lock_guard<std::mutex> lck(d.smallk_mtx);
-	if (d.d_smallk) {
-		if (d.smallk_k == kmer_len && d.smallk_both == (both_strands ? 1u : 0u))
-			return 0;
-		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_open: a table with another kmer_len / both_strands is open on this device");
-	}
-	const size_t bytes = ((size_t)1 << (2 * kmer_len)) * sizeof(u64);
-	u64 *p = nullptr;
-	HIPCHK(hipMalloc((void **)&p, bytes));
-	hipError_t e = hipMemset(p, 0, bytes);
-	if (e == hipSuccess)
-		e = hipDeviceSynchronize();
-	if (e != hipSuccess) {
-		(void)hipFree(p);
-		return fail_hip("hipMemset(small-k table)", e);
-	}
-	d.d_smallk = p;
-	d.smallk_k = kmer_len, d.smallk_both = both_strands ? 1u : 0u;
-	return 0;
+	return accum_open(ctx->devs[dev]->smallk, "kmc_hip_smallk_open", "a small-k table", kmer_len, both_strands ? 1u : 0u, 0, (u64)1 << (2 * kmer_len), sizeof(u64));
 }
 
 int kmc_hip_smallk_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint64_t *dst)
@@ -588,17 +485,7 @@ int kmc_hip_smallk_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t coun
 	if (int rc = set_dev(ctx, dev))
 		return rc;
 	Dev &d = *ctx->devs[dev];
-	std::lock_guard<std::mutex> lck(d.smallk_mtx);
-	if (!d.d_smallk)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_read: no small-k table is open on this device");
-	const uint64_t entries = (uint64_t)1 << (2 * d.smallk_k);
-	if ((count && !dst) || first > entries || count > entries - first)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_read: [first, first + count) lies outside the 4^k entries");
-	if (int rc = estimate_wait_slots(d))
-		return rc;
-	if (count)
-		HIPCHK(hipMemcpy(dst, d.d_smallk + first, (size_t)count * sizeof(u64), hipMemcpyDeviceToHost));
-	return 0;
+	return accum_read(d.smallk, d, "kmc_hip_smallk_read", "small-k table", first, count, dst, sizeof(u64));
 }
 
 int kmc_hip_smallk_close(kmc_hip_ctx *ctx, int dev)
@@ -606,58 +493,33 @@ int kmc_hip_smallk_close(kmc_hip_ctx *ctx, int dev)
 	if (int rc = set_dev(ctx, dev))
 		return rc;
 	Dev &d = *ctx->devs[dev];
-	std::unique_lock<std::mutex> lck(d.smallk_mtx);
-	/* a kmc_hip_smallk_part call holds d_smallk from its check to its return, without the mutex: the table outlives every such call */
-	d.smallk_idle.wait(lck, [&d] { return d.smallk_users == 0; });
-	if (!d.d_smallk)
-		return 0;
-	if (int rc = estimate_wait_slots(d))
-		return rc;
-	HIPCHK(hipFree(d.d_smallk));
-	d.d_smallk = nullptr;
-	d.smallk_k = d.smallk_both = 0;
-	return 0;
+	return accum_close(d.smallk, d);
 }
 
 int kmc_hip_smallk_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint64_t *n_reads, uint64_t *n_kmers)
 {
+	const char *who = "kmc_hip_smallk_part";
 	if (int rc = set_dev(ctx, dev))
 		return rc;
 	if (!p || (size && !text) || !n_reads || !n_kmers || slot < 0 || slot >= N_SLOTS)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: bad argument");
-	if (p->kmer_len < 1 || p->kmer_len > S1_SMALLK_MAX_K || p->file_type > 4 || p->file_type == 3 || p->part_kind > 1)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: unsupported parameters (kmer_len 1..13, file_type 0, 1, 2 or 4, part_kind 0 or 1)");
+	if (p->kmer_len < 1 || p->kmer_len > S1_SMALLK_MAX_K)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: unsupported parameters (kmer_len 1..13)");
 	if (p->flags & ~KMC_HIP_SPLIT_HOMOPOLYMER)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: unknown bit in flags (KMC_HIP_SPLIT_ESTIMATE included: the reference refuses it with small k, kmc.h:773-779)");
-	if ((p->file_type == 2 || p->file_type == 4) && p->part_kind != 0)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: a part of multi-line FASTA (file_type 2) or of BAM records (file_type 4) is a ReadType::na part: part_kind must be 0");
-	if (p->file_type == 4 && size >= S1_BAM_MAX_PART)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: a part of BAM records (file_type 4) must be smaller than 2 GiB");
-	if (p->line_cap < (uint64_t)p->kmer_len + S1_WG_TILE + 2)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: line_cap (mem_part_pmm_reads) is too small for the device splitter: it needs kmer_len + " + std::to_string(S1_WG_TILE + 2) +
-		                                " symbols at least");
+	if (int rc = s1_part_check(who, p, size))
+		return rc;
 	Dev &d = *ctx->devs[dev];
 	u64 *d_table = nullptr;
-	struct TableUser { /* counted from here to the call's return, so that a concurrent kmc_hip_smallk_close cannot free the table in front of the kernel */
-		Dev *d = nullptr;
-		~TableUser()
-		{
-			if (!d)
-				return;
-			std::lock_guard<std::mutex> lck(d->smallk_mtx);
-			if (--d->smallk_users == 0)
-				d->smallk_idle.notify_all();
-		}
-	} table_user;
+	AccumHold table_hold;
 	{
-		std::lock_guard<std::mutex> lck(d.smallk_mtx);
-		if (!d.d_smallk)
+		std::lock_guard<std::mutex> lck(d.smallk.mtx);
+		if (!d.smallk.p)
 			return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part without kmc_hip_smallk_open on this device");
-		if (d.smallk_k != p->kmer_len || d.smallk_both != (p->both_strands ? 1u : 0u))
+		if (d.smallk.par[0] != p->kmer_len || d.smallk.par[1] != (p->both_strands ? 1u : 0u))
 			return fail(KMC_HIP_EINVAL, "kmc_hip_smallk_part: the open table has another kmer_len / both_strands");
-		d_table = d.d_smallk;
-		++d.smallk_users;
-		table_user.d = &d;
+		d_table = (u64 *)d.smallk.p;
+		table_hold.take(d.smallk);
 	}
 	*n_reads = *n_kmers = 0;
 	Slot &s = d.slot[slot];
@@ -665,55 +527,26 @@ int kmc_hip_smallk_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split
 	/* the front half's share of kmc_hip_split_part's work area: text + codes + line ends (multi-line FASTA: sequence starts) + the -hc stream; BAM: two bases per byte */
 	const bool hc = (p->flags & KMC_HIP_SPLIT_HOMOPOLYMER) != 0;
 	const size_t per_byte = p->file_type == 4 ? 8 + (hc ? 4 : 0) : (p->file_type == 2 ? 8 : 6) + (hc ? 2 : 0);
-	if (int rc = ensure(d.s1_arena[slot], (size_t)size * per_byte + ((size_t)32 << 20)))
+	S1Part part;
+	if (int rc = part.begin(d, slot, p, text, size, per_byte))
 		return rc;
-	S1HipBackend be;
-	be.stream = s.stream;
-	be.slot = &s;
-	be.arena = &d.s1_arena[slot];
-	S1PartParams sp;
-	sp.k = p->kmer_len;
-	sp.m = 0, sp.n_bins = 0, sp.max_x = 0; /* the bin path's: not read by the front half */
-	sp.both_strands = p->both_strands ? 1u : 0u;
-	sp.lines_per_record = p->file_type == 1 ? 4u : 2u;
-	sp.multiline_fasta = p->file_type == 2;
-	sp.bam = p->file_type == 4;
-	sp.homopolymer = hc;
-	sp.line_cap = p->line_cap;
-	sp.d_sig_to_bin = nullptr;
-	u32 max_wgs = S1_SMALLK_WGS, lds_k = S1_SMALLK_LDS_K; /* measurement and test switches, like KMC_HIP_S1_SORTED_EMIT: the result does not depend on them */
-	if (const char *e = getenv("KMC_HIP_S1_SMALLK_WGS"))
-		max_wgs = (u32)atoi(e) > 0 ? (u32)atoi(e) : max_wgs;
+	S1HipBackend &be = part.be;
+	/* measurement and test switches, like KMC_HIP_S1_SORTED_EMIT: the result does not depend on them */
+	const u32 max_wgs = env_positive("KMC_HIP_S1_SMALLK_WGS", S1_SMALLK_WGS);
+	u32 lds_k = S1_SMALLK_LDS_K;
 	if (const char *e = getenv("KMC_HIP_S1_SMALLK_LDS_K"))
 		lds_k = (u32)atoi(e) <= S1_SMALLK_LDS_K ? (u32)atoi(e) : lds_k;
 	S1PartResult R;
 	S1Front F;
-	u64 long_reads = 0;
-	if (p->part_kind == 1) {
-		const u64 skip = s1_long_read_title(text, size, p->file_type, long_reads);
-		text += skip;
-		size -= skip;
-		sp.lines_per_record = 0;
-	}
 	try {
-		uint8_t *d_text = (uint8_t *)be.alloc(size + 16);
-		if (size) {
-			hipError_t e = hipMemcpyAsync(d_text, text, size, hipMemcpyHostToDevice, s.stream);
-			if (e != hipSuccess)
-				return fail_hip("hipMemcpyAsync(text)", e);
-		}
-		const int rc = s1_front_part(be, d_text, size, size && text[size - 1] == '\n', sp, R, F, true);
-		if (p->part_kind == 1)
-			R.n_reads = long_reads;
-		if (rc == S1_CHAIN_UNCOVERED)
-			return KMC_HIP_UNCOVERED;
-		if (rc != S1_CHAIN_OK)
-			return R.device_error ? err_to_code(R.device_error) : fail(KMC_HIP_EDEVICE, "kmc_hip_smallk_part: stage-1 chain failed");
+		uint8_t *d_text = part.upload();
+		if (int rc = part.code(who, s1_front_part(be, d_text, part.size, part.ends_with_newline(), part.sp, R, F, true), R))
+			return rc;
 		/* nothing below fails because of the part: only now may its k-mers reach the table */
 		u64 counted = 0;
 		if (F.n >= p->kmer_len) {
 			u64 *d_total = (u64 *)be.alloc(8);
-			s1_smallk_part(be, (const int8_t *)F.d_codes, F.n, p->kmer_len, sp.both_strands, d_table, d_total, max_wgs, lds_k);
+			s1_smallk_part(be, (const int8_t *)F.d_codes, F.n, p->kmer_len, part.sp.both_strands, d_table, d_total, max_wgs, lds_k);
 			be.d2h(&counted, d_total, 8);
 		}
 		*n_kmers = counted;

@@ -175,10 +175,9 @@ void kmc_hip_destroy(kmc_hip_ctx *ctx)
 			(void)hipFree(d->xchg.p);
 		if (d->d_sig_map)
 			(void)hipFree(d->d_sig_map);
-		if (d->d_est)
-			(void)hipFree(d->d_est);
-		if (d->d_smallk)
-			(void)hipFree(d->d_smallk);
+		for (Accum *a : {&d->est, &d->smallk})
+			if (a->p)
+				(void)hipFree(a->p);
 		for (auto &a : d->s1_arena)
 			if (a.p)
 				(void)hipFree(a.p);
@@ -290,11 +289,8 @@ static int sort_records_device_locked(Slot &s, void *d_recs, void *d_tmp, uint64
 	}
 	if (int rc = harvest(s))
 		return rc;
-	u32 err = 0;
-	if (int rc = read_and_clear_sticky(s, err))
-		return rc;
 	*d_result = res;
-	return err_to_code(err);
+	return finish(s);
 }
 
 int kmc_hip_sort_records_device(kmc_hip_ctx *ctx, int dev, void *d_recs, void *d_tmp, uint64_t n, uint32_t words, uint32_t key_bytes,
@@ -371,10 +367,7 @@ static int process_bin_device_on(kmc_hip_ctx *ctx, int dev, Slot &s, const DevPa
 		return rc;
 	if (int rc = harvest(s))
 		return rc;
-	u32 err = 0;
-	if (int rc = read_and_clear_sticky(s, err))
-		return rc;
-	return err_to_code(err);
+	return finish(s);
 }
 
 int kmc_hip_process_bin_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_params *params, const uint8_t *d_superkmers, uint64_t size,
@@ -913,15 +906,7 @@ int kmc_hip_process_bin_multi(kmc_hip_ctx *ctx, const kmc_hip_bin_params *params
 	std::vector<u64> ps;
 	if (int rc = append_pack_starts(P, superkmers, size, pack_bytes, n_packs, ps))
 		return rc;
-	switch ((P.k + 31) / 32) {
-	case 1: return process_bin_multi_t<1>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
-	case 2: return process_bin_multi_t<2>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
-	case 3: return process_bin_multi_t<3>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
-	case 4: return process_bin_multi_t<4>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
-	case 5: return process_bin_multi_t<5>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
-	case 6: return process_bin_multi_t<6>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
-	case 7: return process_bin_multi_t<7>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
-	case 8: return process_bin_multi_t<8>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
-	}
-	return fail(KMC_HIP_EINVAL, "kmer_len out of range");
+	return by_words<8>((P.k + 31) / 32, [&](auto W) {
+		return process_bin_multi_t<decltype(W)::value>(ctx, P, lut_entries, superkmers, size, n_rec, ps, out_suffix, out_capacity, (u64 *)out_bytes, (u64 *)lut, (u64 *)stats);
+	});
 }

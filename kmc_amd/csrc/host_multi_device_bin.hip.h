@@ -124,8 +124,7 @@ int process_bin_multi_t(kmc_hip_ctx *ctx, const DevParams &P, u64 lut_entries, c
 			HIPCHK(hipMemcpy(rec, s.recA.p, SIZE * 8, hipMemcpyDeviceToHost));
 			hist[d][(rec[top >> 3] >> ((top & 7) * 8)) & 0xFF] = 1;
 		}
-		u32 err = 0;
-		if ((rc = read_and_clear_sticky(s, err)) || (rc = err_to_code(err)))
+		if ((rc = finish(s)))
 			return rc;
 	}
 	std::vector<u32> cut((size_t)n_dev + 1, 256); /* device g owns top bytes [cut[g], cut[g+1]) */
@@ -244,8 +243,7 @@ int process_bin_multi_t(kmc_hip_ctx *ctx, const DevParams &P, u64 lut_entries, c
 			return rc;
 		Slot &s = S(g);
 		HIPCHK(hipStreamSynchronize(s.stream));
-		u32 err = 0;
-		if ((rc = read_and_clear_sticky(s, err)) || (rc = err_to_code(err)))
+		if ((rc = finish(s)))
 			return rc;
 		HostRes r;
 		HIPCHK(hipMemcpy(&r, s.zero.p, sizeof r, hipMemcpyDeviceToHost));

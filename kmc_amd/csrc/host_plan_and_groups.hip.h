@@ -307,17 +307,7 @@ template <int SIZE> int sort_only_t(Slot &s, u64 *d_recs, u64 *d_tmp, u64 n, u32
 
 int sort_device(Slot &s, u64 *d_recs, u64 *d_tmp, u64 n, u32 words, u32 n_pass, u64 **d_result, bool stable_lsd)
 {
-	switch (words) {
-	case 1: return sort_only_t<1>(s, d_recs, d_tmp, n, n_pass, d_result, stable_lsd);
-	case 2: return sort_only_t<2>(s, d_recs, d_tmp, n, n_pass, d_result, stable_lsd);
-	case 3: return sort_only_t<3>(s, d_recs, d_tmp, n, n_pass, d_result, stable_lsd);
-	case 4: return sort_only_t<4>(s, d_recs, d_tmp, n, n_pass, d_result, stable_lsd);
-	case 5: return sort_only_t<5>(s, d_recs, d_tmp, n, n_pass, d_result, stable_lsd);
-	case 6: return sort_only_t<6>(s, d_recs, d_tmp, n, n_pass, d_result, stable_lsd);
-	case 7: return sort_only_t<7>(s, d_recs, d_tmp, n, n_pass, d_result, stable_lsd);
-	case 8: return sort_only_t<8>(s, d_recs, d_tmp, n, n_pass, d_result, stable_lsd);
-	}
-	return fail(KMC_HIP_EINVAL, "words must be 1..8");
+	return by_words<8>(words, [&](auto W) { return sort_only_t<decltype(W)::value>(s, d_recs, d_tmp, n, n_pass, d_result, stable_lsd); });
 }
 
 int check_params(const kmc_hip_bin_params *p, DevParams &P)
@@ -1014,18 +1004,7 @@ int run_group_device(Slot &s, const DevParams &P, const kmc_hip_bin_desc *const 
                      bool *used_hybrid = nullptr)
 {
 	bool hyb = false;
-	int rc = KMC_HIP_EINVAL;
-	switch ((P.k + 31) / 32) {
-	case 1: rc = run_group_device_t<1>(s, P, descs, g, lut_entries, classic, d_flag, &hyb); break;
-	case 2: rc = run_group_device_t<2>(s, P, descs, g, lut_entries, classic, d_flag, &hyb); break;
-	case 3: rc = run_group_device_t<3>(s, P, descs, g, lut_entries, classic, d_flag, &hyb); break;
-	case 4: rc = run_group_device_t<4>(s, P, descs, g, lut_entries, classic, d_flag, &hyb); break;
-	case 5: rc = run_group_device_t<5>(s, P, descs, g, lut_entries, classic, d_flag, &hyb); break;
-	case 6: rc = run_group_device_t<6>(s, P, descs, g, lut_entries, classic, d_flag, &hyb); break;
-	case 7: rc = run_group_device_t<7>(s, P, descs, g, lut_entries, classic, d_flag, &hyb); break;
-	case 8: rc = run_group_device_t<8>(s, P, descs, g, lut_entries, classic, d_flag, &hyb); break;
-	default: return fail(KMC_HIP_EINVAL, "kmer_len out of range");
-	}
+	const int rc = by_words<8>((P.k + 31) / 32, [&](auto W) { return run_group_device_t<decltype(W)::value>(s, P, descs, g, lut_entries, classic, d_flag, &hyb); });
 	if (!rc && hyb)
 		g_hybrid_groups.fetch_add(1, std::memory_order_relaxed);
 	if (used_hybrid)

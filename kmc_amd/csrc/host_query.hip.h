@@ -4,10 +4,7 @@ namespace {
 template <int SIZE>
 int db_query_lookup_t(Slot &s, const kmc_hip_db_view &db, u32 k, u32 both, const uint8_t *d_seq, u64 n_bytes, u32 *d_counters, u64 *d_stats)
 {
-	u32 ipt = dq_default_ipt<SIZE>();
-	if (const char *e = getenv("KMC_HIP_QUERY_IPT"))
-		ipt = atoi(e) > 0 ? (u32)atoi(e) : ipt;
-	ipt = std::min(ipt, DQ_IPT_MAX);
+	u32 ipt = std::min(env_positive("KMC_HIP_QUERY_IPT", dq_default_ipt<SIZE>()), DQ_IPT_MAX);
 	while (ipt > 1 && dq_lds_bytes(ipt, k) > 64 * 1024)
 		--ipt;
 	const u64 tile = (u64)DQ_THREADS * ipt, n_tiles = (n_bytes + tile - 1) / tile;
@@ -23,28 +20,23 @@ int kmc_hip_db_query_reads_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_db_vi
                                   const uint64_t *d_read_off, uint64_t n_reads, uint32_t threshold, uint32_t *d_counters, uint32_t *d_n_valid, uint32_t *d_trim_len,
                                   uint8_t *d_masked, uint64_t stats[4])
 {
+	const char *who = "kmc_hip_db_query_reads_device";
 	if (int rc = set_dev(ctx, dev))
 		return rc;
-	if (!db || !stats || !db->d_lut || (db->n_recs && !db->d_recs) || (n_bytes && (!d_seq || !d_counters)))
+	if (!db || !stats || (n_bytes && (!d_seq || !d_counters)))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_query_reads_device: NULL argument");
 	if (!d_read_off && (n_reads || d_n_valid || d_trim_len || d_masked))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_query_reads_device: NULL argument (reads or per-read outputs without a table of read offsets)");
-	if (db->counter_size < 1 || db->counter_size > 4)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_db_query_reads_device: the database's counter_size must be 1..4 (kmc_tools refuses databases without counters, parameters_parser.cpp:788-793)");
-	const u32 p = db->lut_prefix_len;
-	if (p < 1 || p > 15 || p >= kmer_len || (kmer_len - p) % 4)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_db_query_reads_device: (kmer_len - lut_prefix_len) must be a positive multiple of 4, lut_prefix_len 1..15");
-	const u32 words = (kmer_len + 31) / 32;
-	if (words + 1 > 8)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_db_query_reads_device: kmer_len <= 224");
+	if (int rc = check_view(who, db, kmer_len, 1))
+		return rc;
+	if (int rc = check_unpacked_width(who, kmer_len))
+		return rc;
 	if (int rc = kmc_hip_synchronize(ctx, dev)) /* the database may come from asynchronous calls on any stream slot */
 		return rc;
 	Slot &s = ctx->devs[dev]->slot[0];
 	std::lock_guard<std::mutex> lck(s.mtx);
-	u64 last = 0;
-	HIPCHK(hipMemcpy(&last, db->d_lut + ((1ull << (2 * p)) - 1), 8, hipMemcpyDeviceToHost));
-	if (last > db->n_recs)
-		return fail(KMC_HIP_ECORRUPT, "kmc_hip_db_query_reads_device: the database's LUT ends behind its records");
+	if (int rc = check_view_lut(who, db, 1))
+		return rc;
 	for (int q = 0; q < 4; ++q)
 		stats[q] = 0;
 	/* work area: the four tallies [8] | non-zero bits, low bits, their counts per 64 positions [4 x chunks] | the counts' prefix sums [2 x (chunks + 1)] */
@@ -57,20 +49,9 @@ int kmc_hip_db_query_reads_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_db_vi
 	    *low_sum = nz_sum + n_chunks + 1;
 	HIPCHK(hipMemsetAsync(d_stats, 0, 8 * 8, s.stream));
 	s.timed = false;
-	if (n_bytes) {
-		int rc = KMC_HIP_EINVAL;
-		switch (words) {
-		case 1: rc = db_query_lookup_t<1>(s, *db, kmer_len, both_strands ? 1u : 0u, d_seq, n_bytes, d_counters, d_stats); break;
-		case 2: rc = db_query_lookup_t<2>(s, *db, kmer_len, both_strands ? 1u : 0u, d_seq, n_bytes, d_counters, d_stats); break;
-		case 3: rc = db_query_lookup_t<3>(s, *db, kmer_len, both_strands ? 1u : 0u, d_seq, n_bytes, d_counters, d_stats); break;
-		case 4: rc = db_query_lookup_t<4>(s, *db, kmer_len, both_strands ? 1u : 0u, d_seq, n_bytes, d_counters, d_stats); break;
-		case 5: rc = db_query_lookup_t<5>(s, *db, kmer_len, both_strands ? 1u : 0u, d_seq, n_bytes, d_counters, d_stats); break;
-		case 6: rc = db_query_lookup_t<6>(s, *db, kmer_len, both_strands ? 1u : 0u, d_seq, n_bytes, d_counters, d_stats); break;
-		case 7: rc = db_query_lookup_t<7>(s, *db, kmer_len, both_strands ? 1u : 0u, d_seq, n_bytes, d_counters, d_stats); break;
-		}
-		if (rc)
+	if (n_bytes)
+		if (int rc = by_words<7>((kmer_len + 31) / 32, [&](auto W) { return db_query_lookup_t<decltype(W)::value>(s, *db, kmer_len, both_strands ? 1u : 0u, d_seq, n_bytes, d_counters, d_stats); }))
 			return rc;
-	}
 	if (n_reads) {
 		const u64 n_read_blocks = (n_reads + 255) / 256;
 		if (n_read_blocks > 0x7FFFFFFFull)
@@ -92,7 +73,7 @@ int kmc_hip_db_query_reads_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_db_vi
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(s.stream));
 	HIPCHK(hipMemcpy(stats, d_stats, 4 * 8, hipMemcpyDeviceToHost));
-	u32 err = 0;
+	u32 err = 0; /* finish(s), with what KERR_CORRUPT means in this entry in front of err_to_code's words for it */
 	if (int rc = read_and_clear_sticky(s, err))
 		return rc;
 	if (err & KERR_CORRUPT)

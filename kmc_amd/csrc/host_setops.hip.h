@@ -9,10 +9,7 @@ template <int SIZE>
 int db_set_op_t(Slot &s, u32 k, const kmc_hip_db_view &A, const kmc_hip_db_view &B, const SoOp &op, u32 p_out, u32 cs_out, u64 bound, uint8_t *d_out, u64 *d_lut_out, u64 *h_res /* [6] */)
 {
 	constexpr int W = SIZE + 1;
-	u32 ipt = so_default_ipt<SIZE>();
-	if (const char *e = getenv("KMC_HIP_SETOP_IPT"))
-		ipt = atoi(e) > 0 ? (u32)atoi(e) : ipt;
-	ipt = std::min(ipt, SO_IPT_MAX);
+	u32 ipt = std::min(env_positive("KMC_HIP_SETOP_IPT", so_default_ipt<SIZE>()), SO_IPT_MAX);
 	while (ipt > 1 && so_lds_bytes<SIZE>(ipt, true) > 64 * 1024)
 		--ipt;
 	const u64 n = A.n_recs + B.n_recs, tile = (u64)SO_THREADS * ipt, n_tiles = (n + tile - 1) / tile;
@@ -54,37 +51,25 @@ int db_set_op_t(Slot &s, u32 k, const kmc_hip_db_view &A, const kmc_hip_db_view 
 int kmc_hip_db_set_op_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *a, const kmc_hip_db_view *b, const kmc_hip_db_op *op, uint8_t *d_out,
                              uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers, uint64_t stats[6])
 {
+	const char *who = "kmc_hip_db_set_op_device";
 	if (int rc = set_dev(ctx, dev))
 		return rc;
 	if (!a || !b || !op || !d_out || !d_lut_out || !n_kmers || !stats)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_set_op_device: NULL argument");
-	const kmc_hip_db_view *in[2] = {a, b};
-	for (int q = 0; q < 2; ++q) {
-		if (!in[q]->d_lut || (in[q]->n_recs && !in[q]->d_recs))
-			return fail(KMC_HIP_EINVAL, "kmc_hip_db_set_op_device: NULL argument (an input's records or LUT)");
-		if (in[q]->counter_size < 1 || in[q]->counter_size > 4)
-			return fail(KMC_HIP_EINVAL, "kmc_hip_db_set_op_device: an input's counter_size must be 1..4 (kmc_tools refuses databases without counters, parameters_parser.cpp:788-793)");
-	}
-	for (u32 p : {a->lut_prefix_len, b->lut_prefix_len, op->out_lut_prefix_len})
-		if (p < 1 || p > 15 || p >= kmer_len || (kmer_len - p) % 4)
-			return fail(KMC_HIP_EINVAL, "kmc_hip_db_set_op_device: (kmer_len - lut_prefix_len) must be a positive multiple of 4, lut_prefix_len 1..15, for both inputs and the output");
-	const u32 words = (kmer_len + 31) / 32;
-	if (words + 1 > 8)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_db_set_op_device: kmer_len <= 224");
+	int rc = 0;
+	if ((rc = check_view(who, a, kmer_len, 1)) || (rc = check_view(who, b, kmer_len, 1)) || (rc = check_prefix_len(who, "out_lut_prefix_len", op->out_lut_prefix_len, kmer_len)) ||
+	    (rc = check_unpacked_width(who, kmer_len)))
+		return rc;
 	if (op->op >= SO_N_OPS || op->counter_op >= SO_N_CNT)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_set_op_device: unknown operation or counter mode");
 	if (op->cutoff_min < 1 || op->counter_max < 1)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_set_op_device: the output's cutoff_min and counter_max must be at least 1");
-	if (int rc = kmc_hip_synchronize(ctx, dev)) /* the inputs may come from asynchronous calls on any stream slot */
+	if ((rc = kmc_hip_synchronize(ctx, dev))) /* the inputs may come from asynchronous calls on any stream slot */
 		return rc;
 	Slot &s = ctx->devs[dev]->slot[0];
 	std::lock_guard<std::mutex> lck(s.mtx);
-	for (int q = 0; q < 2; ++q) {
-		u64 last = 0;
-		HIPCHK(hipMemcpy(&last, in[q]->d_lut + ((1ull << (2 * in[q]->lut_prefix_len)) - 1), 8, hipMemcpyDeviceToHost));
-		if (last > in[q]->n_recs)
-			return fail(KMC_HIP_ECORRUPT, "kmc_hip_db_set_op_device: an input's LUT ends behind its records");
-	}
+	if ((rc = check_view_lut(who, a, 1)) || (rc = check_view_lut(who, b, 1)))
+		return rc;
 	const u64 na = a->n_recs, nb = b->n_recs;
 	const u64 bound = op->op == SO_UNION ? na + nb : op->op == SO_INTERSECT ? std::min(na, nb) : (op->op == SO_KMERS_SUBTRACT || op->op == SO_COUNTERS_SUBTRACT) ? na : nb;
 	const u32 cs_out = setop_counter_bytes(op->cutoff_max, op->counter_max), rb_out = (kmer_len - op->out_lut_prefix_len) / 4 + cs_out;
@@ -92,21 +77,10 @@ int kmc_hip_db_set_op_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const
 		return fail(KMC_HIP_ECAPACITY, "kmc_hip_db_set_op_device: out_capacity too small for the operation's upper bound (union: both inputs' records; otherwise one input's)");
 	const SoOp so = {op->op, op->counter_op, op->cutoff_min, op->counter_max, op->cutoff_max};
 	s.timed = false;
-	int rc = KMC_HIP_EINVAL;
-	switch (words) {
-	case 1: rc = db_set_op_t<1>(s, kmer_len, *a, *b, so, op->out_lut_prefix_len, cs_out, bound, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 2: rc = db_set_op_t<2>(s, kmer_len, *a, *b, so, op->out_lut_prefix_len, cs_out, bound, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 3: rc = db_set_op_t<3>(s, kmer_len, *a, *b, so, op->out_lut_prefix_len, cs_out, bound, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 4: rc = db_set_op_t<4>(s, kmer_len, *a, *b, so, op->out_lut_prefix_len, cs_out, bound, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 5: rc = db_set_op_t<5>(s, kmer_len, *a, *b, so, op->out_lut_prefix_len, cs_out, bound, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 6: rc = db_set_op_t<6>(s, kmer_len, *a, *b, so, op->out_lut_prefix_len, cs_out, bound, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 7: rc = db_set_op_t<7>(s, kmer_len, *a, *b, so, op->out_lut_prefix_len, cs_out, bound, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	}
-	if (rc)
+	if ((rc = by_words<7>((kmer_len + 31) / 32, [&](auto W) {
+		     return db_set_op_t<decltype(W)::value>(s, kmer_len, *a, *b, so, op->out_lut_prefix_len, cs_out, bound, d_out, (u64 *)d_lut_out, (u64 *)stats);
+	     })))
 		return rc;
 	*n_kmers = stats[KMC_HIP_DB_STAT_WRITTEN];
-	u32 err = 0;
-	if (int rc2 = read_and_clear_sticky(s, err))
-		return rc2;
-	return err_to_code(err);
+	return finish(s);
 }

@@ -1,33 +1,6 @@
 /* kmc_amd/csrc/host_transform.hip.h — part of kmc_hip.hip (included there, not compiled on its own): one database transformed on the device
  * (`kmc_tools transform`: reduce / compact / set_counts / sort, histogram, dump; the kernels are in order_db.hip.h). */
 namespace {
-/* what the three entry points ask of a view; n_seg: segments of its LUT */
-int tr_check_view(const char *who, const kmc_hip_db_view *db, u32 kmer_len, u64 n_seg)
-{
-	std::string w(who);
-	if (!db || !db->d_lut || (db->n_recs && !db->d_recs))
-		return fail(KMC_HIP_EINVAL, w + ": NULL argument (the view, its records or its LUT)");
-	if (db->counter_size < 1 || db->counter_size > 4)
-		return fail(KMC_HIP_EINVAL, w + ": the database's counter_size must be 1..4 (kmc_tools refuses databases without counters, parameters_parser.cpp:788-793)");
-	const u32 p = db->lut_prefix_len;
-	if (p < 1 || p > 15 || p >= kmer_len || (kmer_len - p) % 4)
-		return fail(KMC_HIP_EINVAL, w + ": (kmer_len - lut_prefix_len) must be a positive multiple of 4, lut_prefix_len 1..15");
-	if (n_seg < 1 || (n_seg << (2 * p)) > 0x7FFFFFFFull)
-		return fail(KMC_HIP_EINVAL, w + ": n_lut_segments must be at least 1 and the LUT shorter than 2^31 entries");
-	return 0;
-}
-
-/* the LUT's last entry — and, of a segmented LUT, the closing one behind it — must not lie behind the records */
-int tr_check_lut(const char *who, const kmc_hip_db_view *db, u64 n_seg)
-{
-	const u64 n_entries = n_seg << (2 * db->lut_prefix_len);
-	u64 last[2] = {0, 0};
-	HIPCHK(hipMemcpy(last, db->d_lut + (n_entries - 1), n_seg > 1 ? 16 : 8, hipMemcpyDeviceToHost));
-	if (last[0] > db->n_recs || last[1] > db->n_recs)
-		return fail(KMC_HIP_ECORRUPT, std::string(who) + ": the database's LUT ends behind its records");
-	return 0;
-}
-
 template <int SIZE>
 int db_reduce_t(Slot &s, u32 k, const kmc_hip_db_view &db, const TrCut &cut, u32 p_out, u32 cs_out, uint8_t *d_out, u64 *d_lut_out, u64 *h_res /* [4] */)
 {
@@ -58,14 +31,6 @@ int db_reduce_t(Slot &s, u32 k, const kmc_hip_db_view &db, const TrCut &cut, u32
 	HIPCHK(hipMemcpy(h_res + 3, tile_base + n_tiles, 8, hipMemcpyDeviceToHost));
 	return 0;
 }
-
-int tr_finish(Slot &s)
-{
-	u32 err = 0;
-	if (int rc = read_and_clear_sticky(s, err))
-		return rc;
-	return err_to_code(err);
-}
 } // namespace
 
 int kmc_hip_db_reduce_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *db, uint32_t cutoff_min, uint64_t cutoff_max, uint32_t counter_max,
@@ -76,21 +41,20 @@ int kmc_hip_db_reduce_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const
 		return rc;
 	if (!d_out || !d_lut_out || !n_kmers || !stats)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_reduce_device: NULL argument");
-	if (int rc = tr_check_view(who, db, kmer_len, 1))
+	if (int rc = check_view(who, db, kmer_len, 1))
 		return rc;
 	const u32 p = out_lut_prefix_len;
-	if (p < 1 || p > 15 || p >= kmer_len || (kmer_len - p) % 4)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_db_reduce_device: (kmer_len - out_lut_prefix_len) must be a positive multiple of 4, out_lut_prefix_len 1..15");
-	const u32 words = (kmer_len + 31) / 32;
-	if (words + 1 > 8)
-		return fail(KMC_HIP_EINVAL, "kmc_hip_db_reduce_device: kmer_len <= 224");
+	if (int rc = check_prefix_len(who, "out_lut_prefix_len", p, kmer_len))
+		return rc;
+	if (int rc = check_unpacked_width(who, kmer_len))
+		return rc;
 	if (cutoff_min < 1 || counter_max < 1)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_reduce_device: the output's cutoff_min and counter_max must be at least 1");
 	if (int rc = kmc_hip_synchronize(ctx, dev)) /* the input may come from asynchronous calls on any stream slot */
 		return rc;
 	Slot &s = ctx->devs[dev]->slot[0];
 	std::lock_guard<std::mutex> lck(s.mtx);
-	if (int rc = tr_check_lut(who, db, 1))
+	if (int rc = check_view_lut(who, db, 1))
 		return rc;
 	/* kmc1_db_writer.h:154-156 */
 	const u32 cs_out = counter_value ? setop_counter_bytes(counter_value, counter_value) : setop_counter_bytes(cutoff_max, counter_max), rb_out = (kmer_len - p) / 4 + cs_out;
@@ -98,20 +62,10 @@ int kmc_hip_db_reduce_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const
 		return fail(KMC_HIP_ECAPACITY, "kmc_hip_db_reduce_device: out_capacity too small for the input's records");
 	const TrCut cut = {db->cutoff_min, db->cutoff_max, cutoff_min, cutoff_max, counter_max, counter_value};
 	s.timed = false;
-	int rc = KMC_HIP_EINVAL;
-	switch (words) {
-	case 1: rc = db_reduce_t<1>(s, kmer_len, *db, cut, p, cs_out, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 2: rc = db_reduce_t<2>(s, kmer_len, *db, cut, p, cs_out, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 3: rc = db_reduce_t<3>(s, kmer_len, *db, cut, p, cs_out, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 4: rc = db_reduce_t<4>(s, kmer_len, *db, cut, p, cs_out, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 5: rc = db_reduce_t<5>(s, kmer_len, *db, cut, p, cs_out, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 6: rc = db_reduce_t<6>(s, kmer_len, *db, cut, p, cs_out, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	case 7: rc = db_reduce_t<7>(s, kmer_len, *db, cut, p, cs_out, d_out, (u64 *)d_lut_out, (u64 *)stats); break;
-	}
-	if (rc)
+	if (int rc = by_words<7>((kmer_len + 31) / 32, [&](auto W) { return db_reduce_t<decltype(W)::value>(s, kmer_len, *db, cut, p, cs_out, d_out, (u64 *)d_lut_out, (u64 *)stats); }))
 		return rc;
 	*n_kmers = stats[KMC_HIP_DBT_STAT_WRITTEN];
-	return tr_finish(s);
+	return finish(s);
 }
 
 int kmc_hip_db_histogram_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *db, uint32_t n_lut_segments, uint32_t cutoff_min, uint64_t cutoff_max,
@@ -122,7 +76,7 @@ int kmc_hip_db_histogram_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, co
 		return rc;
 	if (!d_hist || !stats)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_histogram_device: NULL argument");
-	if (int rc = tr_check_view(who, db, kmer_len, n_lut_segments))
+	if (int rc = check_view(who, db, kmer_len, n_lut_segments))
 		return rc;
 	if (cutoff_min < 1 || cutoff_max < cutoff_min || cutoff_max > 0xFFFFFFFFull)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_histogram_device: 1 <= cutoff_min <= cutoff_max < 2^32");
@@ -130,7 +84,7 @@ int kmc_hip_db_histogram_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, co
 		return rc;
 	Slot &s = ctx->devs[dev]->slot[0];
 	std::lock_guard<std::mutex> lck(s.mtx);
-	if (int rc = tr_check_lut(who, db, n_lut_segments))
+	if (int rc = check_view_lut(who, db, n_lut_segments))
 		return rc;
 	if (int rc = ensure(s.bounds, 8 * 8))
 		return rc;
@@ -150,7 +104,7 @@ int kmc_hip_db_histogram_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, co
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(s.stream));
 	HIPCHK(hipMemcpy(stats, d_stats, 3 * 8, hipMemcpyDeviceToHost));
-	return tr_finish(s);
+	return finish(s);
 }
 
 int kmc_hip_db_dump_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *db, uint32_t n_lut_segments, uint64_t first, uint64_t count, uint32_t cutoff_min,
@@ -161,7 +115,7 @@ int kmc_hip_db_dump_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const k
 		return rc;
 	if (!n_bytes || !stats || (count && !d_text))
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_dump_device: NULL argument");
-	if (int rc = tr_check_view(who, db, kmer_len, n_lut_segments))
+	if (int rc = check_view(who, db, kmer_len, n_lut_segments))
 		return rc;
 	if (cutoff_min < 1 || counter_max < 1)
 		return fail(KMC_HIP_EINVAL, "kmc_hip_db_dump_device: the output's cutoff_min and counter_max must be at least 1");
@@ -175,11 +129,9 @@ int kmc_hip_db_dump_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const k
 		return rc;
 	Slot &s = ctx->devs[dev]->slot[0];
 	std::lock_guard<std::mutex> lck(s.mtx);
-	if (int rc = tr_check_lut(who, db, n_lut_segments))
+	if (int rc = check_view_lut(who, db, n_lut_segments))
 		return rc;
-	u32 tile = tr_default_tile(kmer_len);
-	if (const char *e = getenv("KMC_HIP_DUMP_TILE")) /* records of a tile (tests: a few hundred, so that a small database crosses tile seams) */
-		tile = atoi(e) > 0 ? (u32)atoi(e) : tile;
+	u32 tile = env_positive("KMC_HIP_DUMP_TILE", tr_default_tile(kmer_len)); /* records of a tile (tests: a few hundred, so that a small database crosses tile seams) */
 	tile = std::max(1u, std::min(tile, TR_IMAGE_MAX / (kmer_len + TR_REC_EXTRA)));
 	const u64 n_tiles = (count + tile - 1) / tile;
 	if (n_tiles > 0x7FFFFFFFull)
@@ -203,5 +155,5 @@ int kmc_hip_db_dump_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const k
 	HIPCHK(hipMemcpy(n_bytes, tile_base + n_tiles, 8, hipMemcpyDeviceToHost));
 	/* records written = the range's records less the three kinds that are not */
 	stats[KMC_HIP_DBT_STAT_WRITTEN] = count - stats[0] - stats[1] - stats[2];
-	return tr_finish(s);
+	return finish(s);
 }

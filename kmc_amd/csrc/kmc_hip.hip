@@ -23,6 +23,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/kmc_hip.h"
@@ -234,6 +235,34 @@ struct Slot {
 	bool without_output = false;
 };
 
+/* A device array that stage-1 part calls add into, one per device and kind (the estimator's counters, the small-k table): opened with parameters — the same ones
+ * open it again as a no-op, others are refused —, read by range once the slots' streams are idle, closed only when no part call holds it (accum_* below). */
+struct Accum {
+	void *p = nullptr; /* nullptr = none open */
+	u32 par[3] = {0, 0, 0}; /* what it was opened with */
+	u64 entries = 0;
+	u32 users = 0; /* part calls that took p (AccumHold) and have not returned: the close waits for them */
+	std::mutex mtx;
+	std::condition_variable idle;
+};
+/* A part call holds the array from its check of the parameters, under a.mtx, to its return, without the mutex: a concurrent close cannot free it in front of the kernel. */
+struct AccumHold {
+	Accum *a = nullptr;
+	void take(Accum &acc) /* the caller holds acc.mtx */
+	{
+		++acc.users;
+		a = &acc;
+	}
+	~AccumHold()
+	{
+		if (!a)
+			return;
+		std::lock_guard<std::mutex> lck(a->mtx);
+		if (--a->users == 0)
+			a->idle.notify_all();
+	}
+};
+
 struct Dev {
 	int ordinal = 0;
 	u32 rr = 0; /* round-robin slot choice of asynchronous device-resident calls (under rr_mtx) */
@@ -245,16 +274,8 @@ struct Dev {
 	u32 sig_map_entries = 0;
 	std::mutex map_mtx;
 	DBuf s1_arena[N_SLOTS]; /* stage 1: grow-only work area of kmc_hip_split_part, one per stream slot */
-	u32 *d_est = nullptr;   /* stage 1: the two counter arrays of kmc_hip_estimate_open (type 0, then type 1: 2^est_r entries each); nullptr = none open */
-	u32 est_k = 0, est_s = 0, est_r = 0;
-	u32 est_users = 0; /* kmc_hip_split_part calls that took d_est and have not returned: kmc_hip_estimate_close waits for them */
-	std::mutex est_mtx;
-	std::condition_variable est_idle;
-	u64 *d_smallk = nullptr; /* stage 1, small k: the 4^smallk_k counters of kmc_hip_smallk_open; nullptr = none open */
-	u32 smallk_k = 0, smallk_both = 0;
-	u32 smallk_users = 0; /* kmc_hip_smallk_part calls that took d_smallk and have not returned: kmc_hip_smallk_close waits for them */
-	std::mutex smallk_mtx;
-	std::condition_variable smallk_idle;
+	Accum est;    /* stage 1: the two u32 counter arrays of kmc_hip_estimate_open (type 0, then type 1: 2^r entries each); par: kmer_len, s, r */
+	Accum smallk; /* stage 1, small k: the 4^k u64 counters of kmc_hip_smallk_open; par: kmer_len, both_strands */
 };
 
 u32 counter_bytes(u64 cutoff_max, u64 counter_max) { return kmc_counter_bytes(cutoff_max, counter_max); }
@@ -270,6 +291,26 @@ struct kmc_hip_ctx {
 };
 
 namespace {
+
+/* The one dispatch on the record width: f(std::integral_constant<int, W>) with W == words, and what it returns; KMC_HIP_EINVAL for a width outside 1..MAX. MAX is 8
+ * (k <= 256) for the entries that count, 7 for kmc_hip_order_database_device and the database family, whose records are SIZE + 1 words (k <= 224): no width above
+ * MAX is instantiated. Kernel launches stay in the _t functions f calls, not in f itself (tests/emu.py rewrites them textually). */
+template <int MAX, int W = 1, class F> int by_words(u32 words, F &&f)
+{
+	if (words == (u32)W)
+		return f(std::integral_constant<int, W>{});
+	if constexpr (W < MAX)
+		return by_words<MAX, W + 1>(words, f);
+	else
+		return fail(KMC_HIP_EINVAL, "records of " + std::to_string(words) + " words: this entry takes 1.." + std::to_string(MAX));
+}
+
+/* a tuning or test switch: the positive integer in the environment variable `name`, else `dflt` */
+u32 env_positive(const char *name, u32 dflt)
+{
+	const char *e = getenv(name);
+	return e && atoi(e) > 0 ? (u32)atoi(e) : dflt;
+}
 
 int set_dev(kmc_hip_ctx *ctx, int dev)
 {
@@ -302,10 +343,10 @@ template <int SIZE> int set_func_attrs()
 }
 int set_all_func_attrs()
 {
-	int rc = 0;
-	(void)((rc = set_func_attrs<1>()) || (rc = set_func_attrs<2>()) || (rc = set_func_attrs<3>()) || (rc = set_func_attrs<4>()) ||
-	       (rc = set_func_attrs<5>()) || (rc = set_func_attrs<6>()) || (rc = set_func_attrs<7>()) || (rc = set_func_attrs<8>()));
-	return rc;
+	for (u32 words = 1; words <= 8; ++words)
+		if (int rc = by_words<8>(words, [](auto W) { return set_func_attrs<decltype(W)::value>(); }))
+			return rc;
+	return 0;
 }
 
 int slot_init(Slot &s, u64 portion)
@@ -417,6 +458,131 @@ int read_and_clear_sticky(Slot &s, u32 &err)
 		return clear_sticky(s, err);
 	return 0;
 }
+
+int err_to_code(u32 err); /* host_plan_and_groups.hip.h */
+/* the end of a synchronous entry whose stream is idle: the slot's sticky word, read and cleared, as the return code */
+int finish(Slot &s)
+{
+	u32 err = 0;
+	if (int rc = read_and_clear_sticky(s, err))
+		return rc;
+	return err_to_code(err);
+}
+
+/* ---- what the database entries (set operations, filter, transform) ask of a kmc_hip_db_view; `who`: the entry's name; n_seg: segments of the view's LUT ---- */
+int check_prefix_len(const char *who, const char *name, u32 p, u32 kmer_len)
+{
+	if (p < 1 || p > 15 || p >= kmer_len || (kmer_len - p) % 4)
+		return fail(KMC_HIP_EINVAL, std::string(who) + ": (kmer_len - " + name + ") must be a positive multiple of 4, " + name + " 1..15");
+	return 0;
+}
+int check_view(const char *who, const kmc_hip_db_view *db, u32 kmer_len, u64 n_seg)
+{
+	const std::string w(who);
+	if (!db || !db->d_lut || (db->n_recs && !db->d_recs))
+		return fail(KMC_HIP_EINVAL, w + ": NULL argument (a view, its records or its LUT)");
+	if (db->counter_size < 1 || db->counter_size > 4)
+		return fail(KMC_HIP_EINVAL, w + ": a database's counter_size must be 1..4 (kmc_tools refuses databases without counters, parameters_parser.cpp:788-793)");
+	if (int rc = check_prefix_len(who, "lut_prefix_len", db->lut_prefix_len, kmer_len))
+		return rc;
+	if (n_seg < 1 || (n_seg << (2 * db->lut_prefix_len)) > 0x7FFFFFFFull)
+		return fail(KMC_HIP_EINVAL, w + ": n_lut_segments must be at least 1 and the LUT shorter than 2^31 entries");
+	return 0;
+}
+/* the entries that unpack records (SIZE + 1 words, by_words<7>); the histogram and the dump read the packed records and take every kmer_len */
+int check_unpacked_width(const char *who, u32 kmer_len)
+{
+	if ((kmer_len + 31) / 32 + 1 > 8)
+		return fail(KMC_HIP_EINVAL, std::string(who) + ": kmer_len <= 224");
+	return 0;
+}
+/* the LUT's last entry — and, of a segmented LUT, the closing one behind it — must not lie behind the records (read back: the caller's streams are idle) */
+int check_view_lut(const char *who, const kmc_hip_db_view *db, u64 n_seg)
+{
+	const u64 n_entries = n_seg << (2 * db->lut_prefix_len);
+	u64 last[2] = {0, 0};
+	HIPCHK(hipMemcpy(last, db->d_lut + (n_entries - 1), n_seg > 1 ? 16 : 8, hipMemcpyDeviceToHost));
+	if (last[0] > db->n_recs || last[1] > db->n_recs)
+		return fail(KMC_HIP_ECORRUPT, std::string(who) + ": a database's LUT ends behind its records");
+	return 0;
+}
+
+/* ---- Accum: open, read, close (`who`: the entry's name, `what`: the array in the messages' words) ---- */
+int wait_slots(Dev &d) /* what the device's slots have launched adds to the arrays */
+{
+	for (auto &sl : d.slot)
+		if (sl.stream)
+			HIPCHK(hipStreamSynchronize(sl.stream));
+	return 0;
+}
+int accum_open(Accum &a, const char *who, const char *what, u32 p0, u32 p1, u32 p2, u64 entries, size_t entry_bytes)
+{
+	std::lock_guard<std::mutex> lck(a.mtx);
+	if (a.p) {
+		if (a.par[0] == p0 && a.par[1] == p1 && a.par[2] == p2)
+			return 0;
+		return fail(KMC_HIP_EINVAL, std::string(who) + ": " + what + " with other parameters is open on this device");
+	}
+	void *p = nullptr;
+	HIPCHK(hipMalloc(&p, entries * entry_bytes));
+	hipError_t e = hipMemset(p, 0, entries * entry_bytes);
+	if (e == hipSuccess)
+		e = hipDeviceSynchronize();
+	if (e != hipSuccess) {
+		(void)hipFree(p);
+		return fail_hip(who, e);
+	}
+	a.p = p;
+	a.par[0] = p0, a.par[1] = p1, a.par[2] = p2;
+	a.entries = entries;
+	return 0;
+}
+int accum_read(Accum &a, Dev &d, const char *who, const char *what, u64 first, u64 count, void *dst, size_t entry_bytes)
+{
+	std::lock_guard<std::mutex> lck(a.mtx);
+	if (!a.p)
+		return fail(KMC_HIP_EINVAL, std::string(who) + ": no " + what + " is open on this device");
+	if ((count && !dst) || first > a.entries || count > a.entries - first)
+		return fail(KMC_HIP_EINVAL, std::string(who) + ": [first, first + count) lies outside the " + std::to_string(a.entries) + " entries");
+	if (int rc = wait_slots(d))
+		return rc;
+	if (count)
+		HIPCHK(hipMemcpy(dst, (const char *)a.p + first * entry_bytes, (size_t)count * entry_bytes, hipMemcpyDeviceToHost));
+	return 0;
+}
+int accum_close(Accum &a, Dev &d)
+{
+	std::unique_lock<std::mutex> lck(a.mtx);
+	a.idle.wait(lck, [&a] { return a.users == 0; }); /* the array outlives every part call that holds it */
+	if (!a.p)
+		return 0;
+	if (int rc = wait_slots(d))
+		return rc;
+	HIPCHK(hipFree(a.p));
+	a.p = nullptr;
+	a.par[0] = a.par[1] = a.par[2] = 0;
+	a.entries = 0;
+	return 0;
+}
+
+/* temporary device allocations of one call (the test hook and the plan of stage 1's first kernels): freed when the owner goes out of scope */
+struct DevTemps {
+	std::vector<void *> held;
+	DevTemps() = default;
+	DevTemps(const DevTemps &) = delete;
+	DevTemps &operator=(const DevTemps &) = delete;
+	~DevTemps()
+	{
+		for (void *p : held)
+			(void)hipFree(p);
+	}
+	int alloc(void **p, size_t bytes)
+	{
+		HIPCHK(hipMalloc(p, bytes));
+		held.push_back(*p);
+		return 0;
+	}
+};
 
 /* The rest of this translation unit, in the order it is compiled (round 5: one 3 400-line file split along its entry families; no kernel and no statement changed).
  * tests/emu.py build_hostlib inlines these files again before it rewrites the kernel launches for the CPU emulation. */

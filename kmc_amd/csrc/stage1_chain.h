@@ -75,6 +75,27 @@ struct S1Front {
 	u64 n = 0;
 };
 
+/* The part's error word (the high half of word `at` of what was read) against `uncovered`, the bits that mean "malformed in a way the kernels do not cover": such
+ * a bit gives S1_CHAIN_UNCOVERED, any other one R.device_error and S1_CHAIN_DEVICE_ERROR. */
+static inline int s1_classify(u32 err, u32 uncovered, S1PartResult &R)
+{
+	if (err & uncovered)
+		return S1_CHAIN_UNCOVERED;
+	if (err) {
+		R.device_error = err;
+		return S1_CHAIN_DEVICE_ERROR;
+	}
+	return S1_CHAIN_OK;
+}
+/* Reads N words from d_src (be.d2h: waits for everything launched before) and classifies the error word among them. */
+template <class B, size_t N> int s1_read_errors(B &be, u64 (&dst)[N], const u64 *d_src, size_t at, u32 uncovered, S1PartResult &R)
+{
+	static_assert(N >= 1, "");
+	if (!be.d2h(dst, d_src, sizeof dst))
+		return S1_CHAIN_BACKEND_FAILURE;
+	return s1_classify((u32)(dst[at] >> 32), uncovered, R);
+}
+
 /* The front half: text / BAM records / multi-line FASTA -> codes, piece marks, the record check, the -hc compaction, n_reads and n_symbols; the part's error
  * words -> S1_CHAIN_UNCOVERED. Uses of P: k, both_strands, lines_per_record, line_cap and the format switches, nothing of the bin path (m, n_bins, max_x, the map).
  * wait_for_errors: without -hc the record check runs beside whatever the caller launches next and its error word is read with that (the bin path: beside the
@@ -98,7 +119,6 @@ template <class B> int s1_front_part(B &be, const uint8_t *d_text, u64 size, boo
 	const u64 stride = P.line_cap - P.k + 1;
 	u64 n;
 	int8_t *d_codes;
-	u32 err;
 	if (P.bam) {
 		/* ---- BAM records -> codes: the record starts (one chain from offset 0 to the part's end), then the bases. No piece marks: a record of line_cap bases
 		 * or more is not taken */
@@ -110,25 +130,17 @@ template <class B> int s1_front_part(B &be, const uint8_t *d_text, u64 size, boo
 		u64 *d_bstat = (u64 *)be.alloc((size_t)tiles * 8);
 		d_codes = (int8_t *)be.alloc_uninit(out_cap + 16);
 		S1_LAUNCH(B, be, k_s1_bam_chain, dim3(tiles), dim3(S1_BLOCK), d_text, size, d_bstat, d_ticket, d_rec, rec_cap, d_small, d_err);
-		if (!be.d2h(small, d_small, sizeof small))
-			return S1_CHAIN_BACKEND_FAILURE;
-		err = (u32)(small[3] >> 32);
+		if (const int rc = s1_read_errors(be, small, d_small, 3, S1_TEXT_BAD | KERR_CAPACITY, R))
+			return rc;
 		const u64 n_rec = small[0];
-		if (!err && n_rec) {
+		if (n_rec) {
 			const u32 dt = (u32)((n_rec + S1_BLOCK - 1) / S1_BLOCK);
 			u64 *d_dstat = (u64 *)be.alloc((size_t)dt * 8);
 			be.zero(d_ticket, 4);
 			S1_LAUNCH(B, be, k_s1_bam_decode, dim3(dt), dim3(S1_BLOCK), d_text, size, (const u32 *)d_rec, n_rec, P.both_strands, P.line_cap, d_dstat, d_ticket, d_codes, out_cap,
 			          d_small, d_err);
-			if (!be.d2h(small, d_small, sizeof small))
-				return S1_CHAIN_BACKEND_FAILURE;
-			err = (u32)(small[3] >> 32);
-		}
-		if (err & (S1_TEXT_BAD | KERR_CAPACITY))
-			return S1_CHAIN_UNCOVERED;
-		if (err) {
-			R.device_error = err;
-			return S1_CHAIN_DEVICE_ERROR;
+			if (const int rc = s1_read_errors(be, small, d_small, 3, S1_TEXT_BAD | KERR_CAPACITY, R))
+				return rc;
 		}
 		n = n_rec ? small[1] : 0;
 		R.n_symbols = n;
@@ -142,15 +154,8 @@ template <class B> int s1_front_part(B &be, const uint8_t *d_text, u64 size, boo
 		u64 *d_status = (u64 *)be.alloc((size_t)tiles * 24);
 		S1_LAUNCH(B, be, k_s1_ml_text_to_codes, dim3(tiles), dim3(S1_BLOCK), d_text, size, d_status, d_status + tiles, d_status + 2 * (size_t)tiles, d_ticket, d_codes,
 		          d_seq_start, seq_cap, d_small, d_err);
-		if (!be.d2h(small, d_small, sizeof small))
-			return S1_CHAIN_BACKEND_FAILURE;
-		err = (u32)(small[3] >> 32);
-		if (err & (S1_TEXT_BAD | KERR_CAPACITY))
-			return S1_CHAIN_UNCOVERED;
-		if (err) {
-			R.device_error = err;
-			return S1_CHAIN_DEVICE_ERROR;
-		}
+		if (const int rc = s1_read_errors(be, small, d_small, 3, S1_TEXT_BAD | KERR_CAPACITY, R))
+			return rc;
 		n = small[1];
 		R.n_symbols = n;
 		R.n_reads = small[0];
@@ -166,15 +171,8 @@ template <class B> int s1_front_part(B &be, const uint8_t *d_text, u64 size, boo
 		u64 *d_status = (u64 *)be.alloc((size_t)tiles * 16);
 		S1_LAUNCH(B, be, k_s1_text_to_codes, dim3(tiles), dim3(S1_BLOCK), d_text, size, lpr, d_status, d_status + tiles, d_ticket, d_codes, d_nl, nl_cap, d_seq_start, d_small,
 		          d_err);
-		if (!be.d2h(small, d_small, sizeof small))
-			return S1_CHAIN_BACKEND_FAILURE;
-		err = (u32)(small[3] >> 32);
-		if (err & (S1_TEXT_BAD | KERR_CAPACITY))
-			return S1_CHAIN_UNCOVERED;
-		if (err) {
-			R.device_error = err;
-			return S1_CHAIN_DEVICE_ERROR;
-		}
+		if (const int rc = s1_read_errors(be, small, d_small, 3, S1_TEXT_BAD | KERR_CAPACITY, R))
+			return rc;
 		const u64 n_lines = small[0];
 		n = small[1];
 		R.n_symbols = n;
@@ -198,15 +196,8 @@ template <class B> int s1_front_part(B &be, const uint8_t *d_text, u64 size, boo
 		be.zero(d_ticket, 4);
 		S1_LAUNCH(B, be, k_s1_hc_compact, dim3(ht), dim3(S1_BLOCK), (const int8_t *)d_codes, n, P.k, d_hstat, d_ticket, d_hc, hc_cap, d_small + 5, d_err);
 		u64 hc[3]; /* ticket, error word | has_marks | compacted codes */
-		if (!be.d2h(hc, d_small + 3, sizeof hc))
-			return S1_CHAIN_BACKEND_FAILURE;
-		err = (u32)(hc[0] >> 32);
-		if (err & S1_TEXT_BAD)
-			return S1_CHAIN_UNCOVERED; /* the record check ran beside the compaction */
-		if (err) {
-			R.device_error = err;
-			return S1_CHAIN_DEVICE_ERROR;
-		}
+		if (const int rc = s1_read_errors(be, hc, d_small + 3, 0, S1_TEXT_BAD, R)) /* S1_TEXT_BAD: the record check ran beside the compaction */
+			return rc;
 		d_codes = d_hc;
 		n = hc[2];
 		d_cut_marks = nullptr;
@@ -214,15 +205,8 @@ template <class B> int s1_front_part(B &be, const uint8_t *d_text, u64 size, boo
 	F.d_small = d_small, F.d_has_marks = d_has_marks, F.d_ticket = d_ticket, F.d_err = d_err;
 	F.d_cut_marks = d_cut_marks, F.d_codes = d_codes, F.n = n;
 	if (wait_for_errors && !(P.homopolymer && n)) { /* the -hc block has just read the word */
-		if (!be.d2h(small, d_small, sizeof small))
-			return S1_CHAIN_BACKEND_FAILURE;
-		err = (u32)(small[3] >> 32);
-		if (err & S1_TEXT_BAD)
-			return S1_CHAIN_UNCOVERED;
-		if (err) {
-			R.device_error = err;
-			return S1_CHAIN_DEVICE_ERROR;
-		}
+		if (const int rc = s1_read_errors(be, small, d_small, 3, S1_TEXT_BAD, R))
+			return rc;
 	}
 	return S1_CHAIN_OK;
 }
@@ -281,12 +265,8 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 			return S1_CHAIN_BACKEND_FAILURE;
 		err = (u32)(small[3] >> 32);
 	}
-	if (err & S1_TEXT_BAD)
-		return S1_CHAIN_UNCOVERED; /* the record check ran beside the cut */
-	if (err) {
-		R.device_error = err;
-		return S1_CHAIN_DEVICE_ERROR;
-	}
+	if (const int rc = s1_classify(err, S1_TEXT_BAD, R)) /* S1_TEXT_BAD: the record check ran beside the cut */
+		return rc;
 	R.n_superkmers = n_sk;
 	/* ---- per-bin sums, layout, records */
 	u64 *d_tot = (u64 *)be.alloc((size_t)4 * nb * 8); /* bytes | super-k-mers | k-mers | n_plus_x_recs */
@@ -300,13 +280,10 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 	}
 	S1_LAUNCH(B, be, k_s1_bin_layout, dim3(1), dim3(256), (const u64 *)d_tot, nb, d_lay, d_lay + nb + 1, d_lay + 2 * nb + 2, (u64 *)nullptr);
 	std::vector<u64> lay(2 * (size_t)nb + 2);
-	if (!be.d2h(lay.data(), d_lay, lay.size() * 8) || !be.d2h(small, d_small, sizeof small))
+	if (!be.d2h(lay.data(), d_lay, lay.size() * 8))
 		return S1_CHAIN_BACKEND_FAILURE;
-	err = (u32)(small[3] >> 32);
-	if (err) { /* a signature the map does not know (KERR_CORRUPT from k_s1_bin_totals): nothing is emitted */
-		R.device_error = err;
-		return S1_CHAIN_DEVICE_ERROR;
-	}
+	if (const int rc = s1_read_errors(be, small, d_small, 3, 0, R)) /* a signature the map does not know (KERR_CORRUPT from k_s1_bin_totals): nothing is emitted */
+		return rc;
 	const u64 recs_bytes = lay[nb], n_packs = lay[2 * (size_t)nb + 1];
 	uint8_t *d_recs = (uint8_t *)be.alloc(recs_bytes + 16);
 	u64 *d_packs = (u64 *)be.alloc((n_packs + 1) * 8);
@@ -333,13 +310,10 @@ template <class B> int s1_split_part(B &be, const uint8_t *d_text, u64 size, boo
 		          (const u64 *)(d_lay + nb + 1), (const u64 *)d_cum, d_estat, d_ticket, d_recs, d_packs, d_err);
 	}
 	std::vector<u64> tot(4 * (size_t)nb);
-	if (!be.d2h(tot.data(), d_tot, tot.size() * 8) || !be.d2h(small, d_small, sizeof small))
+	if (!be.d2h(tot.data(), d_tot, tot.size() * 8))
 		return S1_CHAIN_BACKEND_FAILURE;
-	err = (u32)(small[3] >> 32);
-	if (err) {
-		R.device_error = err;
-		return S1_CHAIN_DEVICE_ERROR;
-	}
+	if (const int rc = s1_read_errors(be, small, d_small, 3, 0, R))
+		return rc;
 	for (u32 b = 0; b < nb; ++b) {
 		R.bin_off[b] = lay[b];
 		R.bin_bytes[b] = tot[b];
