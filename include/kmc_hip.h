@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 #define KMC_HIP_ABI_VERSION 4 /* 3: + kmc_hip_process_bins_submit/_wait (bound by the worker's loader), kmc_hip_process_bin_multi, kmc_hip_order_database_device;
-                               * 4: kmc_hip_split_params.part_kind (long-read parts); symbols added since keep it: kmc_hip_db_set_op_device, kmc_hip_db_query_reads_device */
+                               * 4: kmc_hip_split_params.part_kind (long-read parts); symbols added since keep it: kmc_hip_db_set_op_device, kmc_hip_db_query_reads_device,
+                               * kmc_hip_db_expr_device */
 
 enum {
 	KMC_HIP_OK = 0,
@@ -310,6 +311,42 @@ int kmc_hip_db_histogram_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, co
                                 uint64_t *d_hist, uint64_t stats[3]);
 int kmc_hip_db_dump_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *db, uint32_t n_lut_segments, uint64_t first, uint64_t count, uint32_t cutoff_min,
                            uint64_t cutoff_max, uint32_t counter_max, uint8_t *d_text, uint64_t text_capacity, uint64_t *n_bytes, uint64_t stats[4]);
+
+/* ---- a set expression over several ordered databases ---------------------------------------------------
+ * `kmc_tools complex <operations_definition_file>` on the device: n_views database bodies as above (kmer_len <= 224, each view with its own input cutoffs) and ONE
+ * expression over them, given as a postfix program of n_steps steps:
+ *   kind KMC_HIP_DB_EXPR_INPUT: push the input views[arg];
+ *   kind KMC_HIP_DB_INTERSECT | _UNION | _KMERS_SUBTRACT | _COUNTERS_SUBTRACT: pop the right side, pop the left side, push the node; arg is the node's counter mode
+ *     KMC_HIP_DB_CNT_* (ignored by KMERS_SUBTRACT).
+ * An input may be named by several steps; every such occurrence is a LEAF, and a program has at most KMC_HIP_DB_EXPR_MAX_LEAVES of them.
+ * Semantics, node by node as the reference evaluates its tree (kmc_tools/expression_node.h, operations.h):
+ *   leaf: the records of the input whose counter lies in the view's [cutoff_min, cutoff_max] (kmc1_db_reader.h:574-576,618);
+ *   inner node: counters are uint32. A k-mer in both sides: INTERSECT, UNION and COUNTERS_SUBTRACT give it the counter min / max / sum (wraps) / left / right of the
+ *     two; mode DIFF gives left - right if left > right and NO record otherwise (C2ArgOper::EqualsToOuputBundle, operations.h:40-68); KMERS_SUBTRACT drops it
+ *     (:174-205). A k-mer in one side only: UNION keeps it from either side (:91-127), the two subtractions keep the left side's (:174-205, :221-255), INTERSECT
+ *     drops it (:139-161). No cutoff and no clamp inside the tree;
+ *   root: the writer's rule and nothing else (kmc1_db_writer.h:382-385): a counter below out->cutoff_min (>= 1) or above out->cutoff_max is dropped and tallied, what
+ *     is left is clamped to out->counter_max (>= 1).
+ * `out` is a kmc_hip_db_op whose op and counter_op are ignored: cutoff_min, cutoff_max, counter_max and out_lut_prefix_len of the output. d_out, d_lut_out, the counter
+ * bytes and *n_kmers are as kmc_hip_db_set_op_device leaves them. A program of one INPUT step is legal (`out = a`: transform reduce).
+ * out_capacity (bytes) must hold the tree's own upper bound, computed from the inputs' n_recs: UNION left + right, INTERSECT the smaller side, the subtractions the left
+ * side — KMC_HIP_ECAPACITY otherwise. KMC_HIP_EINVAL: a NULL argument; a malformed program (no steps, an input index >= n_views, an unknown kind or counter mode, a
+ * stack underflow, not exactly one value left); more leaves than KMC_HIP_DB_EXPR_MAX_LEAVES; a view that kmc_hip_db_set_op_device would refuse; out->cutoff_min or
+ * out->counter_max below 1. KMC_HIP_ECORRUPT: a LUT whose last entry exceeds n_recs; inputs that are not ordered sets, found when a tile of the key space holds more
+ * records than the partition's bound allows (nothing of that tile is written). Synchronous.
+ * stats[5]: distinct k-mers present in at least one leaf; k-mers the root holds before the writer's rule; of those, dropped below cutoff_min / above cutoff_max; written.
+ * $KMC_HIP_EXPR_TILE: records of a tile of the key space (downwards only; default: 32 KiB of LDS per workgroup).
+ * Replaces: the tree of CUnion / CIntersection / CKmersSubtract / CCountersSubtract bundles (operations.h:85-256), one thread per node passing bundles through queues,
+ * feeding CKMC1DbWriter<SIZE>::add_kmer. A chain of kmc_hip_db_set_op_device calls is NOT equivalent: every call there applies the writer's rule. */
+#define KMC_HIP_DB_EXPR_INPUT 16u     /* kmc_hip_db_expr_step.kind of a leaf */
+#define KMC_HIP_DB_EXPR_MAX_LEAVES 16 /* the value stack of a right-deep tree is then 16 registers of the tile kernel, and the leaves' pointers and lengths fit its arguments */
+enum { KMC_HIP_DBX_STAT_KEYS = 0, KMC_HIP_DBX_STAT_RESULT = 1, KMC_HIP_DBX_STAT_BELOW_MIN = 2, KMC_HIP_DBX_STAT_ABOVE_MAX = 3, KMC_HIP_DBX_STAT_WRITTEN = 4 };
+typedef struct kmc_hip_db_expr_step {
+	uint32_t kind; /* KMC_HIP_DB_EXPR_INPUT, or KMC_HIP_DB_INTERSECT .. KMC_HIP_DB_COUNTERS_SUBTRACT */
+	uint32_t arg;  /* INPUT: index into views; otherwise KMC_HIP_DB_CNT_MIN .. _RIGHT */
+} kmc_hip_db_expr_step;
+int kmc_hip_db_expr_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *views, uint32_t n_views, const kmc_hip_db_expr_step *steps, uint32_t n_steps,
+                           const kmc_hip_db_op *out, uint8_t *d_out, uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers, uint64_t stats[5]);
 
 /* ---- end-of-run tallies ---------------------------------------------------------------------- */
 

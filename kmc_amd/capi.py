@@ -103,10 +103,19 @@ class DbOp(C.Structure):
 # KMC_HIP_DB_*: the operations of `kmc_tools simple` and its -oc counter modes, by the names the command line uses
 DB_OPS = {"intersect": 0, "union": 1, "kmers_subtract": 2, "counters_subtract": 3, "reverse_kmers_subtract": 4, "reverse_counters_subtract": 5}
 DB_COUNTER_OPS = {"min": 0, "max": 1, "sum": 2, "diff": 3, "left": 4, "right": 5}
+class DbExprStep(C.Structure):
+    """struct kmc_hip_db_expr_step: one step of the postfix program of kmc_hip_db_expr_device"""
+
+    _fields_ = [("kind", C.c_uint32), ("arg", C.c_uint32)]
+
+
+DB_EXPR_INPUT = 16  # KMC_HIP_DB_EXPR_INPUT
+DB_EXPR_MAX_LEAVES = 16  # KMC_HIP_DB_EXPR_MAX_LEAVES
 DB_STATS = ("n_pairs", "n_only_a", "n_only_b", "n_below_min", "n_above_max", "n_written")  # stats[] of kmc_hip_db_set_op_device, in order
 DBQ_STATS = ("n_valid_windows", "n_found", "n_cut", "n_invalid_windows")  # stats[] of kmc_hip_db_query_reads_device, in order
 DBT_STATS = ("n_cut_in", "n_below_min", "n_above_max", "n_written")  # stats[] of kmc_hip_db_reduce_device and kmc_hip_db_dump_device, in order
 DBH_STATS = ("n_cut_in", "n_outside", "n_counted")  # stats[] of kmc_hip_db_histogram_device, in order
+DBX_STATS = ("n_keys", "n_result", "n_below_min", "n_above_max", "n_written")  # stats[] of kmc_hip_db_expr_device, in order
 
 
 def make_params(k, both_strands=1, cutoff_min=2, cutoff_max=10**9, counter_max=255, lut_prefix_len=3, output_type=0,
@@ -131,6 +140,7 @@ SYMBOLS = [
     "kmc_hip_smallk_open", "kmc_hip_smallk_part", "kmc_hip_smallk_read", "kmc_hip_smallk_close",
     "kmc_hip_db_set_op_device", "kmc_hip_db_query_reads_device",
     "kmc_hip_db_reduce_device", "kmc_hip_db_histogram_device", "kmc_hip_db_dump_device",
+    "kmc_hip_db_expr_device",
 ]
 
 _LIB = None
@@ -228,6 +238,8 @@ def load():
         L.kmc_hip_db_reduce_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, u64p, u64p]
         L.kmc_hip_db_histogram_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint32, C.c_uint64, vp, u64p]
         L.kmc_hip_db_dump_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, u64p]
+    if hasattr(L, "kmc_hip_db_expr_device"):  # added within ABI version 4
+        L.kmc_hip_db_expr_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.POINTER(DbExprStep), C.c_uint32, C.POINTER(DbOp), vp, C.c_uint64, vp, u64p, u64p]
     _LIB = L
     return L
 
@@ -512,6 +524,15 @@ class Context:
         self._chk(self.L.kmc_hip_db_dump_device(self.h, dev, kmer_len, C.byref(db), n_lut_segments, first, count, cutoff_min, cutoff_max, counter_max, d_text or None, text_capacity,
                                                 C.byref(n), st))
         return n.value, dict(zip(DBT_STATS, (int(x) for x in st)))
+
+    def db_expr_device(self, kmer_len: int, views, steps, out: DbOp, d_out: int, out_capacity: int, d_lut_out: int, dev: int = 0):
+        """One `kmc_tools complex` expression over device-resident KMC1 bodies (kmc_hip_db_expr_device). views: DbView's; steps: the postfix program as (kind, arg) pairs
+        (expr_steps makes them); out: a DbOp whose op and counter_op are ignored. Returns (records written, dict of DBX_STATS)."""
+        self._need("kmc_hip_db_expr_device")
+        va, sa = (DbView * max(len(views), 1))(*views), (DbExprStep * max(len(steps), 1))(*[DbExprStep(*s) for s in steps])
+        n, st = C.c_uint64(), (C.c_uint64 * 5)()
+        self._chk(self.L.kmc_hip_db_expr_device(self.h, dev, kmer_len, va, len(views), sa, len(steps), C.byref(out), d_out, out_capacity, d_lut_out, C.byref(n), st))
+        return n.value, dict(zip(DBX_STATS, (int(x) for x in st)))
 
     def host_alloc(self, nbytes: int) -> np.ndarray:
         """Pinned host memory as a uint8 array (free with host_free(arr))."""

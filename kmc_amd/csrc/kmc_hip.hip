@@ -595,3 +595,4 @@ struct DevTemps {
 #include "host_setops.hip.h" /* set operations between two ordered databases (`kmc_tools simple`) */
 #include "host_query.hip.h" /* the reads of a file against an ordered database (`kmc_tools filter`) */
 #include "host_transform.hip.h" /* one database reduced, histogrammed or dumped as text (`kmc_tools transform`) */
+#include "host_expr.hip.h" /* a set expression over several ordered databases (`kmc_tools complex`) */

@@ -19,6 +19,11 @@
  *                   classified only-in-A / only-in-B / pair, operation + counter mode + the writer's cutoffs and clamp applied; run twice — <false> counts the
  *                   kept records of the tile and the six tallies, k_db_cumsum scans the counts, <true> writes the kept records at their offsets
  * and k_db_pack packs the result for the output's lut_prefix_len and counter size.
+ *
+ * A set expression over SEVERAL such databases (`kmc_tools complex`): every named input through k_db_unpack once, then
+ *   k_cx_partition  one thread per sample (every S-th record of every leaf): its rank among all samples; every M-th sample by rank is a tile's splitter
+ *   k_cx_tile       one workgroup per tile of the key space: every leaf's slice in LDS, the postfix program walked once per record — <false> counts, <true> writes
+ * and k_db_pack as above (the comment in front of the kernels has the partition's bound and its proof).
  */
 #ifndef KMC_AMD_ORDER_DB_HIP_H
 #define KMC_AMD_ORDER_DB_HIP_H
@@ -887,6 +892,280 @@ __global__ void __launch_bounds__(TR_THREADS) k_tr_dump(const uint8_t *__restric
 		dst16[i] = src16[i];
 	for (u32 i = tail0 + tid; i < total; i += TR_THREADS)
 		dst[i] = img[i];
+}
+
+/* ---- a set expression over several ordered databases (`kmc_tools complex`) ----
+ * kmc_tools/operations.h:40-256 (the nodes), expression_node.h (the tree), kmc1_db_writer.h:382-385 (the root). Every operation is pointwise per k-mer: whether a
+ * k-mer is in a node's result, and with which counter, depends only on whether it is in the node's two children and with which counters. So the key space is cut into
+ * tiles, every LEAF's (occurrence of an input in the expression) slice of a tile is brought into LDS, and the postfix program is walked once per record.
+ *
+ * k_cx_partition. Every S-th record of every leaf (indices 0, S, 2S, ...) is a sample. Samples are ordered by (key, leaf); a sample's rank is the number of samples in
+ * front of it, found by one binary search per leaf. Every M-th sample by rank is a splitter and writes, per leaf, the lower bound of its key. Tile t holds the keys in
+ * [splitter t, splitter t + 1) (the last tile: everything from its splitter on), so (i) equal keys lie in one tile and every slice is a lower-bound range.
+ * (ii), (iii): a tile's slices hold at most S (M + 2L - 1) - L records, L the number of leaves. Proof. Let the tile be the keys in [x_a, x_b), its splitters' ranks r_a and
+ * r_b = r_a + M. A sample with a key in that range sorts before (x_b, leaf of b), so its rank is below r_b; if its rank is below r_a its key is x_a and its leaf lies in
+ * front of a's leaf — keys are distinct inside a leaf, so there are at most L - 1 of those. The range holds at most M + L - 1 samples. Leaf l's slice is a run of
+ * record indices that holds m_l multiples of S, hence at most (m_l + 1) S - 1 records (it starts behind the multiple in front and ends before the next one).
+ * Summed: S (sum of m_l + L) - L <= S (M + 2L - 1) - L. The host takes M = 2L and S = (T + L) / (4L - 1): never more than T records (half of T on average).
+ * The rank-0 sample is the smallest record of all, so tile 0 starts at record 0 of every leaf.
+ *
+ * k_cx_tile. LDS: the slices, T records of SIZE + 1 words, and (WRITE) one 64-bit word per merged rank. The default T keeps both at 32 KiB together for every record
+ * width (cx_default_tile: 1365 records of one key word ... 455 of seven) — five workgroups on a CU's 160 KiB; $KMC_HIP_EXPR_TILE overrides downwards (not below
+ * CX_MIN_TILE). A tile whose slices hold more than T records writes nothing and raises stats[CX_ST_FLAG]: LDS is never overrun.
+ * The value stack is a presence bit mask and a register array that is SHIFTED on every push and pop, so every index is static: no scratch. */
+#ifndef CX_THREADS
+#define CX_THREADS 256 /* threads of a k_cx_tile workgroup */
+#endif
+/* leaf occurrences of an expression (KMC_HIP_DB_EXPR_MAX_LEAVES). 16: the stack of a right-deep tree is then 16 registers, the leaves' pointers and lengths 256 bytes of
+ * kernel arguments, and at the narrowest default tile (455 records) S is still 7 */
+constexpr u32 CX_MAX_LEAVES = 16;
+constexpr u32 CX_MAX_STEPS = 2 * CX_MAX_LEAVES - 1;
+constexpr u32 CX_MIN_TILE = 64; /* >= 3 L - 1 for L = 16: S >= 1 */
+constexpr u32 CX_INPUT = 16;    /* KMC_HIP_DB_EXPR_INPUT */
+enum : u32 { CX_ST_KEYS = 0, CX_ST_RESULT = 1, CX_ST_BELOW_MIN = 2, CX_ST_ABOVE_MAX = 3, CX_ST_FLAG = 5 };
+template <int SIZE> constexpr u32 cx_default_tile() { return 32 * 1024 / ((SIZE + 2) * 8); }
+template <int SIZE> constexpr size_t cx_lds_bytes(u32 tile, bool write) { return (size_t)tile * (SIZE + 1) * 8 + (write ? (size_t)tile * 8 : 0); }
+
+struct CxLeaves {
+	const u64 *rec[CX_MAX_LEAVES]; /* the leaf's input, unpacked */
+	u64 n[CX_MAX_LEAVES];
+	u64 first_sample[CX_MAX_LEAVES + 1]; /* samples of the leaves in front */
+	u32 n_leaves;
+};
+struct CxProg {
+	u32 n_steps;
+	u32 step[CX_MAX_STEPS]; /* CX_INPUT, or SO_INTERSECT | SO_UNION | SO_KMERS_SUBTRACT | SO_COUNTERS_SUBTRACT, the counter mode << 8 */
+};
+struct CxOut {
+	u32 cutoff_min, counter_max;
+	u64 cutoff_max;
+};
+
+/* records of s[0 .. n) with a key below x */
+template <int SIZE> __device__ __forceinline__ u64 cx_lower_bound(const u64 *s, u64 n, const u64 *x)
+{
+	u64 lo = 0, hi = n;
+	while (lo < hi) {
+		const u64 mid = (lo + hi) >> 1;
+		if (so_less<SIZE>(s + mid * (SIZE + 1), x))
+			lo = mid + 1;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+
+template <int SIZE>
+__global__ void __launch_bounds__(256) k_cx_partition(CxLeaves lv, u32 S, u32 M, u64 n_samples, u64 n_tiles, u64 *__restrict__ bounds /* [n_tiles + 1][n_leaves] */)
+{
+	constexpr int W = SIZE + 1;
+	const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
+	const u32 L = lv.n_leaves;
+	if (g < L)
+		bounds[n_tiles * L + g] = lv.n[g]; /* the end of the last tile */
+	if (g >= n_samples)
+		return;
+	u32 mine = 0;
+	while (mine + 1 < L && g >= lv.first_sample[mine + 1])
+		++mine;
+	const u64 j = g - lv.first_sample[mine];
+	u64 x[SIZE];
+	{
+		const u64 *r = lv.rec[mine] + j * S * W;
+#pragma unroll
+		for (int w = 0; w < SIZE; ++w)
+			x[w] = r[w];
+	}
+	u64 rank = j;
+	for (u32 l = 0; l < L; ++l) {
+		if (l == mine)
+			continue;
+		u64 lb = cx_lower_bound<SIZE>(lv.rec[l], lv.n[l], x);
+		if (l < mine && lb < lv.n[l] && so_equal<SIZE>(lv.rec[l] + lb * W, x))
+			++lb; /* a leaf in front: its sample of the same key sorts before this one */
+		rank += (lb + S - 1) / S; /* samples at the indices 0, S, .. below lb */
+	}
+	if (rank % M)
+		return;
+	u64 *o = bounds + rank / M * L;
+	for (u32 l = 0; l < L; ++l)
+		o[l] = l == mine ? j * S : cx_lower_bound<SIZE>(lv.rec[l], lv.n[l], x);
+}
+
+/* one operation node on (present, counter) of its children: C2ArgOper::EqualsToOuputBundle for a pair (DIFF with c1 <= c2 inserts nothing), the loops of
+ * CUnion / CIntersection / CKmersSubtract / CCountersSubtract for what is in one child only */
+__device__ __forceinline__ bool cx_node(u32 kind, u32 mode, bool p1, u32 c1, bool p2, u32 c2, u32 &c)
+{
+	if (p1 && p2) {
+		c = so_counter(mode, c1, c2);
+		return kind != SO_KMERS_SUBTRACT && !(mode == SO_CNT_DIFF && c1 <= c2);
+	}
+	c = p1 ? c1 : c2;
+	return p1 ? kind != SO_INTERSECT : (p2 && kind == SO_UNION);
+}
+
+/* WRITE = false: tile_count[tile] = records the tile keeps, stats[0..3] += its tallies. WRITE = true: the kept records, in key order, to out[tile_base[tile] ..]. */
+template <int SIZE, bool WRITE>
+__global__ void __launch_bounds__(CX_THREADS) k_cx_tile(CxLeaves lv, CxProg pg, const u64 *__restrict__ bounds, u32 T, CxOut wr, const u64 *__restrict__ tile_base,
+                                                       u64 *__restrict__ tile_count, u64 *__restrict__ out, u64 out_cap /* records */, u64 *__restrict__ stats)
+{
+	constexpr int W = SIZE + 1;
+	KMC_DYN_LDS(u64, cx_lds);
+	__shared__ u32 s_off[CX_MAX_LEAVES + 1];
+	__shared__ u32 s_scan[CX_THREADS / 64 + 1];
+	__shared__ u32 s_bad;
+	const u32 tid = threadIdx.x, L = lv.n_leaves;
+	const u64 t = blockIdx.x;
+	const u64 *b0 = bounds + t * L, *b1 = b0 + L;
+	u64 *s_rec = cx_lds, *s_slot = cx_lds + (size_t)T * W;
+	if (tid == 0) {
+		u32 off = 0, bad = 0;
+		for (u32 l = 0; l < L; ++l) {
+			const u64 lo = b0[l], hi = b1[l];
+			s_off[l] = off;
+			if (hi < lo || hi > lv.n[l] || hi - lo > (u64)(T - off))
+				bad = 1;
+			else
+				off += (u32)(hi - lo);
+		}
+		s_off[L] = off;
+		s_bad = bad;
+	}
+	__syncthreads();
+	if (s_bad) { /* more than the LDS was sized for: nothing is read or written, the entry reports it */
+		if (tid == 0) {
+			atomicOr((unsigned long long *)(stats + CX_ST_FLAG), 1ull);
+			if (!WRITE)
+				tile_count[t] = 0;
+		}
+		return;
+	}
+	const u32 total = s_off[L];
+	for (u32 l = 0; l < L; ++l) { /* runs of whole records: flat, coalesced copies */
+		const u64 *src = lv.rec[l] + b0[l] * W;
+		u64 *dst = s_rec + (size_t)s_off[l] * W;
+		const u32 words = (s_off[l + 1] - s_off[l]) * W;
+		for (u32 g = tid; g < words; g += CX_THREADS)
+			dst[g] = src[g];
+	}
+	if (WRITE)
+		for (u32 g = tid; g < total; g += CX_THREADS)
+			s_slot[g] = 0;
+	__syncthreads();
+	u32 n_keys = 0, n_result = 0, n_below = 0, n_above = 0, kept = 0;
+	for (u32 r = tid; r < total; r += CX_THREADS) {
+		u32 mine = 0;
+		while (r >= s_off[mine + 1])
+			++mine;
+		u64 x[SIZE];
+#pragma unroll
+		for (int w = 0; w < SIZE; ++w)
+			x[w] = s_rec[(size_t)r * W + w];
+		u32 cnt[CX_MAX_LEAVES]; /* the value stack, top at [0]; bit d of pmask: the value at depth d is present */
+#pragma unroll
+		for (u32 d = 0; d < CX_MAX_LEAVES; ++d)
+			cnt[d] = 0;
+		u32 pmask = 0, rank = 0, leaf = 0;
+		bool earlier = false, any = false;
+		for (u32 i = 0; i < pg.n_steps; ++i) {
+			const u32 kind = pg.step[i] & 0xFFu, mode = pg.step[i] >> 8;
+			if (kind == CX_INPUT) {
+				const u32 l = leaf++, base = s_off[l], n = s_off[l + 1] - base;
+				const u64 *sl = s_rec + (size_t)base * W;
+				u32 lb = (u32)cx_lower_bound<SIZE>(sl, n, x);
+				bool hit = lb < n && so_equal<SIZE>(sl + (size_t)lb * W, x);
+				if (l == mine) {
+					lb = r - base;
+					hit = true;
+				}
+				const u64 c = hit ? sl[(size_t)lb * W + SIZE] : SO_ABSENT;
+				const bool present = c != SO_ABSENT;
+				rank += lb + (l < mine && hit ? 1u : 0u); /* equal keys order by leaf */
+				earlier = earlier || (l < mine && hit);
+				any = any || present;
+#pragma unroll
+				for (u32 d = CX_MAX_LEAVES - 1; d > 0; --d)
+					cnt[d] = cnt[d - 1];
+				cnt[0] = present ? (u32)c : 0u;
+				pmask = (pmask << 1) | (present ? 1u : 0u);
+			} else {
+				u32 c;
+				const bool p = cx_node(kind, mode, (pmask & 2u) != 0, cnt[1], (pmask & 1u) != 0, cnt[0], c);
+#pragma unroll
+				for (u32 d = 1; d + 1 < CX_MAX_LEAVES; ++d)
+					cnt[d] = cnt[d + 1];
+				cnt[0] = c;
+				pmask = ((pmask >> 2) << 1) | (p ? 1u : 0u);
+			}
+		}
+		if (earlier) /* not the head of its key's run */
+			continue;
+		n_keys += any ? 1u : 0u;
+		if (!(pmask & 1u))
+			continue;
+		++n_result;
+		u32 c = cnt[0];
+		if (c < wr.cutoff_min) /* kmc1_db_writer.h:382-385 */
+			++n_below;
+		else if ((u64)c > wr.cutoff_max)
+			++n_above;
+		else {
+			++kept;
+			if (c > wr.counter_max)
+				c = wr.counter_max;
+			if (WRITE)
+				s_slot[rank] = (u64)c << 32 | (r + 1);
+		}
+	}
+	if (!WRITE) {
+		const u32 mine4[5] = {n_keys, n_result, n_below, n_above, kept};
+		u32 sums[5];
+#pragma unroll
+		for (int q = 0; q < 5; ++q)
+			sums[q] = wave_sum<u32>(mine4[q]);
+		if ((tid & 63) == 0) {
+#pragma unroll
+			for (int q = 0; q < 4; ++q)
+				if (sums[q])
+					atomicAdd((unsigned long long *)(stats + q), (unsigned long long)sums[q]);
+			s_scan[tid >> 6] = sums[4];
+		}
+		__syncthreads();
+		if (tid == 0) {
+			u32 all = 0;
+			for (u32 q = 0; q < CX_THREADS / 64; ++q)
+				all += s_scan[q];
+			tile_count[t] = all;
+		}
+		return;
+	}
+	__syncthreads();
+	/* compaction in key order: a thread owns a run of merged ranks */
+	const u32 chunk = (total + CX_THREADS - 1) / CX_THREADS;
+	const u32 p0 = tid * chunk < total ? tid * chunk : total, p1 = p0 + chunk < total ? p0 + chunk : total;
+	u32 have = 0;
+	for (u32 p = p0; p < p1; ++p)
+		have += s_slot[p] ? 1u : 0u;
+	u32 all;
+	const u32 first = block_excl_sum<CX_THREADS / 64, u32>(have, s_scan, all);
+	const u64 base = tile_base[t];
+	if (base + all > out_cap) { /* inputs that are not ordered sets: more than the tree's bound */
+		if (tid == 0)
+			atomicOr((unsigned long long *)(stats + CX_ST_FLAG), 2ull);
+		return;
+	}
+	u64 *o = out + (base + first) * W;
+	for (u32 p = p0; p < p1; ++p) {
+		const u64 v = s_slot[p];
+		if (!v)
+			continue;
+		const u64 *src = s_rec + (size_t)((u32)v - 1) * W;
+#pragma unroll
+		for (int w = 0; w < SIZE; ++w)
+			o[w] = src[w];
+		o[SIZE] = v >> 32;
+		o += W;
+	}
 }
 
 #endif

@@ -1,15 +1,17 @@
 """python -m kmc_amd.tools simple <db1> [-ci<v> -cx<v>] <db2> [-ci<v> -cx<v>] <operation> <out> [-ci<v> -cx<v> -cs<v> -oc<mode>] [<operation> <out> ...]
 python -m kmc_amd.tools filter [-t | -hm] <db> [-ci<v> -cx<v>] <reads> [-ci<v> -cx<v> -fa|-fq] <out> [-fa|-fq]
 python -m kmc_amd.tools transform <db> [-ci<v> -cx<v>] <oper> [-s] <out> [-ci<v> -cx<v> -cs<v> -okmc] [<oper> ...]
+python -m kmc_amd.tools complex <operations_definition_file>
 
-`kmc_tools simple`, `kmc_tools filter` and `kmc_tools transform` on the device: the argument order and the defaults are the reference's (kmc_tools/parameters_parser.cpp),
+`kmc_tools simple`, `kmc_tools filter`, `kmc_tools transform` and `kmc_tools complex` on the device: the argument order and the defaults are the reference's (kmc_tools/parameters_parser.cpp),
 the databases, the reads and the text written are byte for byte those kmc_tools writes. simple: one kmc_hip_db_set_op_device call per output. filter: one
 kmc_hip_db_query_reads_device call per part of the reads file. transform: the input uploaded once, then per output kmc_hip_db_reduce_device (reduce, compact, set_counts,
 sort), kmc_hip_db_histogram_device, or kmc_hip_db_dump_device per part of the text. A database as `kmc` wrote it (KMC2) is ordered on the device first — by transform
-only when an output needs the order."""
+only when an output needs the order. complex: every input the expression names uploaded once, then ONE kmc_hip_db_expr_device call for the whole expression."""
 from __future__ import annotations
 
 import os
+import re
 import sys
 
 import numpy as np
@@ -606,6 +608,281 @@ def transform(argv, ctx=None) -> list:
     return results
 
 
+COMPLEX_USAGE = """usage: python -m kmc_amd.tools complex <operations_definition_file>
+  the file (kmc_tools' format):
+    INPUT:
+    <name> = <db> [-ci<v>] [-cx<v>]     one line per input database; -ci / -cx: k-mers with a counter outside [ci, cx] count as absent
+    ...
+    OUTPUT:
+    <out> = <expression>                 over the names: + union, * intersect (binds tighter), - kmers_subtract, ~ counters_subtract, parentheses; left to right.
+                                         A counter mode min | max | diff | sum | left | right may stand directly behind + ~ * (defaults: + sum, * min, ~ diff)
+    [OUTPUT_PARAMS:
+    -ci<v> -cx<v> -cs<v> -okmc]          cutoffs and counter clamp of <out> (defaults: smallest input -ci, largest input -cx, largest counter the inputs can hold)
+  At most 16 occurrences of inputs in the expression. Counters inside the expression are 32-bit and neither cut nor clamped; only <out> is."""
+COMPLEX_KEYWORDS = ("min", "max", "diff", "sum", "left", "right")  # tokenizer.cpp:28-33, in the order they are tried
+_TOKEN_PATTERNS = [(re.compile(p), t) for p, t in
+                   [(r"\(", "("), (r"\)", ")"), (r"-", "-"), (r"~", "~"), (r"\+", "+"), (r"\*", "*")] + [(kw, kw) for kw in COMPLEX_KEYWORDS] + [(r"\w*", "var")]]
+_EXPR_WHITESPACE = " \t\r\n\v\f"
+_EXPR_OPS = {"+": ("union", "sum"), "-": ("kmers_subtract", "diff"), "~": ("counters_subtract", "diff"), "*": ("intersect", "min")}  # operator -> (operation, default mode)
+
+
+def tokenize_expression(expr: str) -> list:
+    """tokenizer.cpp:50-77 -> [(text, type)]: the patterns in the reference's order, each anchored at the front of what is left — so a keyword matches as a PREFIX
+    (`minx` is `min`, `x`). Where no pattern consumes a character the reference loops for ever (`\\w*` matches the empty string); that is an error here."""
+    tokens = []
+    rest = expr.lstrip(_EXPR_WHITESPACE)
+    while rest:
+        for pat, typ in _TOKEN_PATTERNS:
+            m = pat.match(rest)
+            if m:
+                break
+        if not m.group(0):
+            raise UsageError(f"wrong output format near: {rest}")
+        tokens.append((m.group(0), typ))
+        rest = rest[m.end():].lstrip(_EXPR_WHITESPACE)
+    return tokens
+
+
+def parse_expression(tokens: list, names: dict):
+    """output_parser.h:94-208 -> the tree: ("in", index) | (operation, counter mode, left, right). expr -> term {(+|-|~) [mode] term}; term -> argument {* [mode] argument};
+    argument -> name | ( expr ). Where the reference's argument() returns a null pointer that is dereferenced later, this raises."""
+    if not tokens:
+        raise UsageError("the output's expression is empty")
+    pos = 0
+
+    def cur():
+        return tokens[pos] if pos < len(tokens) else ("", "end")
+
+    def modifier(default):
+        nonlocal pos
+        if cur()[1] in COMPLEX_KEYWORDS:
+            pos += 1
+            return tokens[pos - 1][1]
+        return default
+
+    def argument():
+        nonlocal pos
+        text, typ = cur()
+        if typ == "var":
+            if text not in names:
+                raise UsageError(f"variable {text} was not defined")
+            pos += 1
+            return ("in", names[text])
+        if typ == "(":
+            pos += 1
+            res = expr()
+            if cur()[1] != ")":
+                raise UsageError(f"close parenthesis expected, but {cur()[0] or 'the end of the expression'} found")
+            pos += 1
+            return res
+        raise UsageError(f"an input's name or '(' expected, but {text or 'the end of the expression'} found")
+
+    def term():
+        nonlocal pos
+        left = argument()
+        while cur()[1] == "*":
+            pos += 1
+            mode = modifier("min")
+            left = ("intersect", mode, left, argument())
+        return left
+
+    def expr():
+        nonlocal pos
+        left = term()
+        while cur()[1] in ("+", "-", "~"):
+            op, default = _EXPR_OPS[cur()[1]]
+            pos += 1
+            mode = modifier(default) if op != "kmers_subtract" else default  # no modifier behind '-' (output_parser.h:192-195)
+            left = (op, mode, left, term())
+        return left
+
+    tree = expr()
+    if pos < len(tokens):
+        raise UsageError(f"wrong symbol: {cur()[0]}")
+    return tree
+
+
+def expr_steps(tree) -> list:
+    """the tree as the postfix program of kmc_hip_db_expr_device: [(kind, arg)]"""
+    if tree[0] == "in":
+        return [(capi.DB_EXPR_INPUT, tree[1])]
+    return expr_steps(tree[2]) + expr_steps(tree[3]) + [(capi.DB_OPS[tree[0]], capi.DB_COUNTER_OPS[tree[1]])]
+
+
+_INPUT_LINE = re.compile(r"^\s*([\w+-]*)\s*=\s*(.*)$", re.ASCII)  # parser.cpp:31-32
+_OUTPUT_LINE = re.compile(r"^\s*(.*)\s*=\s*(.*)$", re.ASCII)
+
+
+def parse_complex(text: str) -> dict:
+    """The operations-definition file, split as kmc_tools/parser.cpp splits it -> dict(inputs [(name, path, ci, cx)], path, tree, ci, cx, cs); 0 = not given"""
+    lines = iter([ln for ln in text.split("\n") if ln.strip(_EXPR_WHITESPACE)])  # nextLine: blank lines are skipped
+    for ln in lines:
+        if "INPUT:" in ln:
+            break
+    else:
+        raise UsageError("'INPUT:' missing")
+    ln = next(lines, None)
+    if ln is None or "OUTPUT:" in ln:
+        raise UsageError("None input was defined")
+    inputs, names = [], {}
+    while True:
+        m = _INPUT_LINE.search(ln)
+        if not m:
+            raise UsageError(f"wrong line format: {ln}")
+        name, words = m.group(1), m.group(2).split()
+        if name in names:
+            raise UsageError(f"Name redefinition({name})")
+        if name in COMPLEX_KEYWORDS:
+            raise UsageError(f"`{name}` is not valid name")
+        if not words:
+            raise UsageError(f"file name for {name} was not specified")
+        ci = cx = 0
+        for w in words[1:]:
+            if w.startswith("-ci"):
+                ci = _num(w, "-ci")
+            elif w.startswith("-cx"):
+                cx = _num(w, "-cx")
+            else:
+                raise UsageError(f"Unknow parameter {w} for variable {name}")
+        names[name] = len(inputs)
+        inputs.append((name, words[0], ci, cx))
+        ln = next(lines, None)
+        if ln is None:
+            raise UsageError("'OUTPUT:' missing")
+        if "OUTPUT:" in ln:
+            break
+    ln = next(lines, None)
+    if ln is None or "OUTPUT_PARAMS:" in ln:
+        raise UsageError("None output was defined")
+    m = _OUTPUT_LINE.search(ln)
+    if not m:
+        raise UsageError(f"wrong line format: {ln}")
+    path = m.group(1).rstrip(_EXPR_WHITESPACE)
+    if not path:
+        raise UsageError(f"wrong line format (output file name is not specified): {ln}")
+    tree = parse_expression(tokenize_expression(m.group(2)), names)
+    o = dict(inputs=inputs, path=path, tree=tree, ci=0, cx=0, cs=0)
+    for ln in lines:
+        if "OUTPUT_PARAMS:" not in ln:
+            continue
+        for w in (next(lines, None) or "").split():
+            if w.startswith("-ci"):
+                o["ci"] = _num(w, "-ci")
+            elif w.startswith("-cx"):
+                o["cx"] = _num(w, "-cx")
+            elif w.startswith("-cs"):
+                o["cs"] = _num(w, "-cs")
+            elif w.startswith("-o"):
+                if w[2:5] == "kff":
+                    raise UsageError(f"{w}: KFF output is not written, only KMC databases")
+                if w[2:5] != "kmc":
+                    raise UsageError(f"Unknown output type: {w[2:]}")
+            else:
+                raise UsageError(f"Unknow parameter {w}")
+        break
+    return o
+
+
+def _leaves(tree) -> list:
+    return [tree[1]] if tree[0] == "in" else _leaves(tree[2]) + _leaves(tree[3])
+
+
+def resolve_complex(o: dict, dbs: list) -> dict:
+    """The defaults (parameters_parser.cpp:842-848, 893-916; kmc1_db_writer.h:425-455) over ALL defined inputs, used in the expression or not.
+    dbs: objects with kmer_len, counter_size, min_count, max_count, total_kmers, both_strands -> dict(cuts, ci, cx, cs, cs_bytes, p_out, canonical)"""
+    k = dbs[0].kmer_len
+    for (name, path, _, _), db in zip(o["inputs"], dbs):
+        if db.kmer_len != k:
+            raise UsageError(f"the inputs have different k-mer lengths ({k} and {db.kmer_len})")
+        if db.counter_size == 0:
+            raise UsageError(f"{path}: counter size 0 (a k-mer set without counters) is not supported, as in kmc_tools")
+    cuts = [(ci or db.min_count, cx or db.max_count) for (_, _, ci, cx), db in zip(o["inputs"], dbs)]
+    ci, cx = o["ci"] or min(c[0] for c in cuts), o["cx"] or max(c[1] for c in cuts)
+    cs = o["cs"] or (1 << (8 * max(db.counter_size for db in dbs))) - 1
+    return dict(cuts=cuts, ci=ci, cx=cx, cs=cs, cs_bytes=min(dbio.byte_log(cs), dbio.byte_log(cx)), p_out=max(dbio.best_lut_prefix_len(k, db.total_kmers) for db in dbs),
+                canonical=all(db.both_strands for db in dbs))
+
+
+def _read_header(path: str) -> dbio.Database:
+    """the header of <path>.kmc_pre alone (the fields dbio.read_database reads from it): what an input contributes that the expression does not name"""
+    with open(path + ".kmc_pre", "rb") as f:
+        f.seek(0, os.SEEK_END)
+        size = f.tell()
+        f.seek(max(size - 256, 0))
+        tail = np.frombuffer(f.read(), dtype=np.uint8)
+    if size < 16 or bytes(tail[-4:]) != b"KMCP" or int(tail[-8:-4].copy().view(np.uint32)[0]) + 8 > tail.size:
+        raise dbio.DbFormatError(f"{path}.kmc_pre: no KMCP markers")
+    header_offset = int(tail[-8:-4].copy().view(np.uint32)[0])
+    kmc2 = int(tail[-12:-8].copy().view(np.uint32)[0]) == 0x200
+    h = tail[tail.size - 8 - header_offset: tail.size - 8]
+    u32 = lambda o: int(h[o:o + 4].copy().view(np.uint32)[0])  # noqa: E731
+    o = 20 if kmc2 else 16
+    return dbio.Database(u32(0), u32(4), u32(8), u32(12), u32(16) if kmc2 else 0, u32(o), (u32(o + 20) << 32) + u32(o + 4), int(h[o + 8:o + 16].copy().view(np.uint64)[0]),
+                         int(h[o + 16]) != 1, kmc2)
+
+
+def _tree_bound(tree, n) -> int:
+    if tree[0] == "in":
+        return n[tree[1]]
+    lt, rt = _tree_bound(tree[2], n), _tree_bound(tree[3], n)
+    return lt + rt if tree[0] == "union" else min(lt, rt) if tree[0] == "intersect" else lt
+
+
+def complex(argv, ctx=None) -> dict:  # noqa: A001 (the mode's name)
+    """Runs the operations-definition file argv[0]; returns the dict of tallies of kmc_hip_db_expr_device."""
+    if len(argv) != 1 or argv[0].startswith("-"):
+        raise UsageError(COMPLEX_USAGE)
+    try:
+        with open(argv[0]) as f:
+            o = parse_complex(f.read())
+    except OSError as e:
+        raise UsageError(f"cannot open file: {argv[0]} ({e.strerror})")
+    leaves = _leaves(o["tree"])
+    if len(leaves) > capi.DB_EXPR_MAX_LEAVES:
+        raise UsageError(f"the expression names inputs {len(leaves)} times; at most {capi.DB_EXPR_MAX_LEAVES} are evaluated")
+    used = sorted(set(leaves))
+    dbs = []
+    for i, (_, path, _, _) in enumerate(o["inputs"]):
+        try:
+            if dbio.is_kff(path) and not os.path.exists(path + ".kmc_pre"):
+                raise UsageError(f"{path}: a KFF file; only KMC databases are read")
+            dbs.append(dbio.read_database(path) if i in used else _read_header(path))  # an input that is defined but not used: its header only
+        except (dbio.DbFormatError, OSError) as e:
+            raise UsageError(str(e))
+    r = resolve_complex(o, dbs)
+    k = dbs[0].kmer_len
+    own = ctx is None
+    if own:
+        ctx = capi.Context((0,))
+    dev = {}
+    try:
+        for i in used:
+            dev[i] = _DeviceDb(ctx, dbs[i])
+        # the views of the inputs the expression names, and the program over those
+        slot = {i: q for q, i in enumerate(used)}
+        views = [dev[i].view(*r["cuts"][i]) for i in used]
+        steps = [(kind, slot[arg] if kind == capi.DB_EXPR_INPUT else arg) for kind, arg in expr_steps(o["tree"])]
+        rb = (k - r["p_out"]) // 4 + r["cs_bytes"]
+        bound = _tree_bound(o["tree"], {i: dev[i].n for i in used})
+        d_out, d_lut = ctx.malloc(bound * rb + 256), ctx.malloc(8 << (2 * r["p_out"]))
+        try:
+            n, st = ctx.db_expr_device(k, views, steps, capi.DbOp(0, 0, r["ci"], r["cs"], r["cx"], r["p_out"]), d_out, bound * rb, d_lut)
+            recs, lut = np.zeros(n * rb, dtype=np.uint8), np.zeros(1 << (2 * r["p_out"]), dtype=np.uint64)
+            if n:
+                ctx.d2h(recs, d_out)
+            ctx.d2h(lut, d_lut)
+        finally:
+            ctx.free(d_out)
+            ctx.free(d_lut)
+        dbio.write_kmc1(o["path"], k, r["cs_bytes"], r["p_out"], r["ci"], r["cx"], r["canonical"], lut, recs, mode=dbs[0].mode)
+    finally:
+        for d in dev.values():
+            d.free()
+        if own:
+            ctx.close()
+    return st
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if argv and argv[0] == "filter":
@@ -619,8 +896,13 @@ def main(argv=None) -> int:
         for (o, st) in zip(outs, sts):
             print(f"{o['op']} -> {o['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
         return 0
+    if argv and argv[0] == "complex":
+        st = complex(argv[1:])
+        print(f"complex -> {parse_complex(open(argv[1]).read())['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
+        return 0
     if not argv or argv[0] != "simple":
-        raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...\n" + FILTER_USAGE + "\n" + TRANSFORM_USAGE)
+        raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...\n" + FILTER_USAGE + "\n" + TRANSFORM_USAGE + "\n"
+                         + COMPLEX_USAGE)
     for (o, st) in zip(parse_simple(argv[1:])[1], simple(argv[1:])):
         print(f"{o['op']} -> {o['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
     return 0
