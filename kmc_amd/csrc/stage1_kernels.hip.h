@@ -3,7 +3,8 @@
  * codes -> minimizer signatures -> super-k-mers -> bin records + the collector's sums. Reachable through kmc_hip_split_part (one part, host
  * text -> host records: the engine of the stage-1 worker plug-in), kmc_hip_split_reads_plan/_emit (codes in HBM -> bins in HBM in the layout
  * kmc_hip_process_bins_device takes) and the test hook kmc_hip_debug_split_reads. The signature -> bin map is an input (stage 0 stays the
- * reference's). GPU-validated: signatures, cut, bin totals / layout / emit; under emulation only so far: text -> codes, record check, k+x sums.
+ * reference's). GPU-validated against the reference's restatement, per part (tests/test_gpu_stage1_parts.py and the per-variant files beside it) and per
+ * kernel (tests/test_gpu_stage1.py): every kernel of this file, at signature lengths 5..11, minimum windows of 1..252 m-mers and k up to 256.
  *
  * What the reference does (kmc_core/splitter.cpp:557-672, CSplitter::ProcessReads) is a sequential scan per read with a two-variable state
  * (current signature, its position). Its RESULT has a data-parallel description, which oracle/stage1_oracle.c's line-by-line restatement
@@ -536,8 +537,8 @@ __global__ void __launch_bounds__(256) k_s1_emit(const int8_t *__restrict__ code
 }
 
 /* ------------------------------------------------------------------------------------------------ text -> codes, k+x-mer sums
- * The two kernels a HIP KmcSplitEngine (kmc_amd/host/split_engine.h) still needs. EMULATION-TESTED ONLY (tests/test_stage1_emulated.py): written
- * after the round's GPU budget was spent, launched by no host code yet.
+ * The front of the part chain (stage1_chain.h, s1_front_part) and the third per-bin sum: launched by kmc_hip_split_part for every plain FASTA / FASTQ part.
+ * Tested under emulation (tests/test_stage1_emulated.py, tests/test_stage1_parts_emulated.py) and on the device (tests/test_gpu_stage1_parts.py).
  *
  * k_s1_text_to_codes: one part of FASTA (lines_per_record 2) or FASTQ (4) text as the reference's readers cut it — it starts at a record's
  * title (fastq_reader.cpp) — to the code stream the kernels above take: the symbols of every sequence line (splitter.cpp:41-47: ACGT acgt ->
@@ -1676,7 +1677,8 @@ __global__ void __launch_bounds__(256) k_s1_bin_plus_x(const int8_t *__restrict_
  * (index << 16) | bin, the EXISTING k_onesweep sorts them by their two low bytes (stable: a bin keeps read order, like the reference with one
  * splitter thread) — and k_s1_emit_sorted gives every record its final position from one exclusive scan of the record sizes in that order:
  *   position = bin_base[bin] + (bytes of all records before it in sorted order) - (bytes of all bins before its bin),
- * so consecutive threads write consecutive bytes. EMULATION-TESTED ONLY, not the default (S1PartParams::sorted_emit): to be measured first. */
+ * so consecutive threads write consecutive bytes. Tested under emulation and on the device (tests/test_gpu_stage1_parts.py: every bin byte for byte in read
+ * order); not the default (S1PartParams::sorted_emit, $KMC_HIP_S1_SORTED_EMIT): to be measured first. */
 __global__ void __launch_bounds__(256) k_s1_sort_keys(const u32 *__restrict__ sk_sig, u64 n_sk, const int *__restrict__ sig_to_bin, u32 n_bins, u64 *__restrict__ keys, u32 *err)
 {
 	const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;

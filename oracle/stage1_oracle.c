@@ -186,11 +186,20 @@ uint32_t oracle_s1_pack(const int8_t *seq, uint32_t n, uint32_t kmer_len, uint8_
 int64_t oracle_s1_split_all(const int8_t *seqs, const uint64_t *seq_off, uint64_t n_seq, uint32_t kmer_len, uint32_t signature_len, uint32_t *sig, uint64_t *rec_off,
                             uint8_t *recs, uint64_t cap_sk, uint64_t cap_bytes)
 {
-	uint32_t *norm = (uint32_t *)malloc(sizeof(uint32_t) << (2 * signature_len));
-	if (!norm || oracle_s1_norm(signature_len, norm)) {
-		free(norm);
-		return -2;
+	/* the table is kept from call to call (tests call this read by read; 4^11 entries take longer to fill than a read to split). Callers are single-threaded. */
+	static uint32_t *kept_norm;
+	static uint32_t kept_len;
+	if (!kept_norm || kept_len != signature_len) {
+		free(kept_norm);
+		kept_norm = (uint32_t *)malloc(sizeof(uint32_t) << (2 * signature_len));
+		if (!kept_norm || oracle_s1_norm(signature_len, kept_norm)) {
+			free(kept_norm);
+			kept_norm = NULL;
+			return -2;
+		}
+		kept_len = signature_len;
 	}
+	const uint32_t *norm = kept_norm;
 	uint64_t n = 0, bytes = 0;
 	oracle_s1_superkmer *tmp = (oracle_s1_superkmer *)malloc(sizeof(oracle_s1_superkmer) * 65536);
 	for (uint64_t s = 0; s < n_seq; ++s) {
@@ -198,13 +207,11 @@ int64_t oracle_s1_split_all(const int8_t *seqs, const uint64_t *seq_off, uint64_
 		const uint32_t qn = (uint32_t)(seq_off[s + 1] - seq_off[s]);
 		const uint64_t m = oracle_s1_split(q, qn, kmer_len, signature_len, norm, tmp, 65536);
 		if (m > 65536 || n + m > cap_sk) {
-			free(norm);
 			free(tmp);
 			return -1;
 		}
 		for (uint64_t i = 0; i < m; ++i) {
 			if (bytes + 1 + (tmp[i].len + 3) / 4 > cap_bytes) {
-				free(norm);
 				free(tmp);
 				return -1;
 			}
@@ -215,7 +222,6 @@ int64_t oracle_s1_split_all(const int8_t *seqs, const uint64_t *seq_off, uint64_
 		}
 	}
 	rec_off[n] = bytes;
-	free(norm);
 	free(tmp);
 	return (int64_t)n;
 }

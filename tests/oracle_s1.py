@@ -40,10 +40,17 @@ def lib():
     return _LIB
 
 
+_NORM = {}
+
+
 def norm_table(sig_len: int) -> np.ndarray:
-    t = np.zeros(1 << (2 * sig_len), dtype=np.uint32)
-    assert lib().oracle_s1_norm(sig_len, t.ctypes.data) == 0
-    return t
+    """CMmer's table of 4^sig_len entries; made once per length (split_stream is called read by read) and read-only"""
+    if sig_len not in _NORM:
+        t = np.zeros(1 << (2 * sig_len), dtype=np.uint32)
+        assert lib().oracle_s1_norm(sig_len, t.ctypes.data) == 0
+        t.flags.writeable = False
+        _NORM[sig_len] = t
+    return _NORM[sig_len]
 
 
 def encode(seqs):
@@ -60,7 +67,9 @@ def split(seqs, k: int, sig_len: int = 9):
     codes, off = encode(seqs)
     total = int(off[-1])
     cap_sk = total + len(seqs) + 16
-    cap_bytes = total + 2 * cap_sk + 64
+    # a record of k + x symbols is 1 + ceil((k + x) / 4) <= 3 + k // 4 + x // 4 bytes, and the x of all records together are fewer than the symbols:
+    # room for a super-k-mer at every position, which is what k = m comes close to
+    cap_bytes = cap_sk * (3 + k // 4) + total // 4 + 64
     sig = np.zeros(cap_sk, dtype=np.uint32)
     rec_off = np.zeros(cap_sk + 1, dtype=np.uint64)
     recs = np.zeros(cap_bytes, dtype=np.uint8)

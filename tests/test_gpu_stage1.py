@@ -1,5 +1,7 @@
-"""-m gpu: the first stage-1 kernels on the device (kmc_hip_debug_split_reads) against the stage-1 oracle, which tests/test_stage1_oracle.py
-pins to the reference. Groundwork for SURVEY.md §8f rank 2 — these kernels are not part of the drop-in yet."""
+"""-m gpu: the stage-1 kernels on the device, below the part entry: signatures and the cut with stored signatures (kmc_hip_debug_split_reads), the fused cut,
+the per-bin sums and the emit on a code stream in HBM (kmc_hip_split_reads_plan / _emit), against the stage-1 oracle, which tests/test_stage1_oracle.py pins
+to the reference. Over the signature lengths 5..11, minimum windows from 1 to 252 m-mers and k up to 256. The same kernels inside the drop-in's part entry
+(kmc_hip_split_part): tests/test_gpu_stage1_parts.py and the per-variant files beside it."""
 import numpy as np
 import pytest
 
@@ -17,7 +19,8 @@ def ctx():
     c.close()
 
 
-@pytest.mark.parametrize("k,m,n_reads", [(27, 9, 400), (21, 9, 200), (55, 9, 200), (14, 7, 100), (200, 9, 60), (28, 11, 100)])
+@pytest.mark.parametrize("k,m,n_reads", [(27, 9, 400), (21, 9, 200), (55, 9, 200), (14, 7, 100), (200, 9, 60), (28, 11, 100), (9, 9, 100), (14, 11, 100), (15, 11, 100),
+                                         (27, 5, 100), (27, 6, 100), (27, 8, 100), (27, 10, 100), (256, 5, 60), (256, 11, 60)])
 def test_stage1_kernels_match_the_oracle(ctx, k, m, n_reads):
     rng = np.random.default_rng(k * 10 + m)
     codes = _stream(_reads(rng, k, n_reads, 150))
@@ -93,10 +96,11 @@ def _records(img, k):
     return out
 
 
-@pytest.mark.parametrize("k,m,n_bins,n_reads", [(27, 9, 512, 20_000), (55, 9, 64, 8_000), (21, 7, 2000, 8_000), (27, 9, 1, 30_000)])
+@pytest.mark.parametrize("k,m,n_bins,n_reads", [(27, 9, 512, 20_000), (55, 9, 64, 8_000), (21, 7, 2000, 8_000), (27, 9, 1, 30_000), (14, 11, 64, 4000),
+                                                (256, 5, 16, 2000)])
 def test_bins_made_on_the_device_hold_the_oracles_records(ctx, k, m, n_bins, n_reads):
     rng = np.random.default_rng(k + n_bins)
-    reads = _genome_reads(rng, n_reads, 200_000)
+    reads = _genome_reads(rng, n_reads, 200_000, 150 if k < 150 else k + 150)  # reads that hold k-mers at every k
     codes = _stream(reads)
     smap = _sig_map(m, n_bins, 5)
     r = _split_on_device(ctx, codes, k, m, smap, n_bins)
