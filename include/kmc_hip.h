@@ -27,7 +27,7 @@ extern "C" {
 
 #define KMC_HIP_ABI_VERSION 4 /* 3: + kmc_hip_process_bins_submit/_wait (bound by the worker's loader), kmc_hip_process_bin_multi, kmc_hip_order_database_device;
                                * 4: kmc_hip_split_params.part_kind (long-read parts); symbols added since keep it: kmc_hip_db_set_op_device, kmc_hip_db_query_reads_device,
-                               * kmc_hip_db_expr_device */
+                               * kmc_hip_db_expr_device, kmc_hip_count_* */
 
 enum {
 	KMC_HIP_OK = 0,
@@ -546,6 +546,58 @@ int kmc_hip_smallk_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t b
 int kmc_hip_smallk_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint64_t *n_reads, uint64_t *n_kmers);
 int kmc_hip_smallk_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint64_t *dst);
 int kmc_hip_smallk_close(kmc_hip_ctx *ctx, int dev);
+
+/* ---- a counting session: reads in, one ordered database body out, no bin record leaves the device (added within ABI version 4, like kmc_hip_smallk_*) ----
+ * The reference carries every part's bin records from stage 1 to stage 2 through the host: CKmerBinStorer appends each collector's buffer to its bin's file
+ * (kb_storer.cpp), CKmerBinReader reads every file back as one bin image (kb_reader.h:141-190), the completer hands the sorted bins on (kb_completer.cpp:160-320). A
+ * session keeps them in HBM instead: kmc_hip_count_part is kmc_hip_split_part up to the records and leaves them in the session's store; kmc_hip_count_finish gathers
+ * the (part, bin) segments into whole bins (k_cnt_gather), runs stage 2 on them where they lie and keeps the bins' outputs; kmc_hip_count_order merges those into the
+ * body `kmc <in> <db> <tmp>` followed by `kmc_tools transform <db> sort <out>` writes, as a kmc_hip_db_view. All occurrences of a canonical k-mer share one signature and
+ * so one bin: the result depends neither on the signature map, nor on n_bins, nor on where the parts are cut. One device per session; k <= 13 has kmc_hip_smallk_*.
+ * Ask kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_COUNT) first.
+ * _open  : replaces the opening of the bin files (CKmerBinStorer::OpenFiles, kb_storer.cpp). Fixes kmer_len, signature_len, n_bins and both_strands of `p` for the
+ *          session; max_x is taken as 0; the signature map is the one kmc_hip_split_set_map uploaded for `dev`. KMC_HIP_EINVAL for the parameters kmc_hip_split_part
+ *          refuses and for kmer_len > 224 (kmc_hip_order_database_device's limit).
+ * _part  : replaces CSplitter::ProcessReads + the collectors for one part, as kmc_hip_split_part does, and CKmerBinStorer::PutBinToTmpFile for its buffers
+ *          (kb_storer.cpp): every file_type (0, 1, 2, 4), part_kind and KMC_HIP_SPLIT_HOMOPOLYMER; KMC_HIP_SPLIT_ESTIMATE, and a part whose kmer_len, signature_len,
+ *          n_bins or both_strands differ from the session's, are KMC_HIP_EINVAL. The part's records are copied device to device into the store: HBM chunks
+ *          ($KMC_HIP_COUNT_CHUNK_MB each, default 256; 0: a chunk per part), a part larger than a chunk gets one of its own, a part's records lie in one chunk. A call
+ *          that does not return 0 (KMC_HIP_UNCOVERED, KMC_HIP_ENOMEM when the store cannot grow, a device error) leaves the session exactly as it was. Calls on
+ *          different slots may run at once; calls on one slot are serialised.
+ * _finish: replaces CKmerBinReader (kb_reader.h:141-190: one image per bin, its expander packs) and the sorters' hand-over to the completer (kb_completer.cpp:160-320).
+ *          Once per session, synchronous, no _part may be running. Lays the bins out (256-byte aligned images, one expander pack per non-empty (part, bin) segment: any
+ *          run of whole records is a legal pack, queues.h:376-396), gathers, frees the store, then runs kmc_hip_process_bins_device over the bins in index order, in
+ *          batches whose worst-case outputs (n_rec x kmc_hip_out_rec_bytes) fit an arena — a quarter of the free device memory, or $KMC_HIP_COUNT_ARENA_MB (0: a bin
+ *          per batch); a bin beyond the arena is a batch of its own, KMC_HIP_ENOMEM before anything of it is launched if that does not fit either — and keeps each bin's
+ *          output in a tight store. bp: kmer_len and both_strands of the session, output_type 0, without_output 0; lut_prefix_len (> 0) is the bins' own and
+ *          invisible in the result. stats[4]: the sum of the bins' tallies in KMC_HIP_STAT_* order; totals[4]: reads, super-k-mers, k-mers entering stage 2, bytes of
+ *          bin records; *n_records: the records stage 2 kept (what a caller chooses out_lut_prefix_len by). A session without a single k-mer finishes with zeros.
+ *          KMC_HIP_EINVAL while a _part call is running. After an error behind the gather the session can only be closed; one in front of it leaves the session as it was.
+ * _order : replaces kmc_tools' sort of the completer's database (CKMC1DbWriter fed by a priority queue over the bins). After _finish, any number of times: allocates
+ *          body and LUT for out_lut_prefix_len (owned by the session, replaced by the next _order), runs kmc_hip_order_database_device over the bins' outputs and
+ *          fills *view: d_recs, n_recs, d_lut, lut_prefix_len, counter_size = kmc_hip_counter_size(cutoff_max, counter_max), and the cutoffs of bp — every record
+ *          lies inside them, so the view goes to every kmc_hip_db_* entry as it is. (With a cutoff_min above counter_max the clamped counters lie below cutoff_min and
+ *          the view, like the header the reference writes for such a run, hides every record from a reader that applies the cutoffs.) KMC_HIP_EINVAL before _finish and for (kmer_len - out_lut_prefix_len) % 4 != 0.
+ * _info  : info[6] = parts in the store, chunks of the store, table entries the gather copied, stage-2 batches, k-mers of the largest bin, bins that are not empty
+ *          (the last four after _finish; diagnostics, the front end's balance figure, tests).
+ * _timings: seconds[4] of the session's last _finish and _order: layout, allocations and uploads of _finish (wall clock); k_cnt_gather (HIP events around the launch);
+ *          stage 2 with the copies into the tight store (wall clock); the last _order (wall clock). What tools/count_bench.py reports.
+ * _close : replaces CKmerBinStorer::Release and the removal of the bin files (kb_storer.cpp): frees everything, in any state; kmc_hip_destroy closes open sessions.
+ *          _part after _finish and a second _finish are KMC_HIP_EINVAL. */
+#define KMC_HIP_SPLIT_COVERS_COUNT 0x105u /* kmc_hip_count_open / _part / _finish / _order / _info / _timings / _close (0x104 stays unknown, as 0x101 does: callers of libraries
+                                           * from before the session use it as the capability that answers 0) */
+typedef struct kmc_hip_count kmc_hip_count; /* one counting session on one device */
+int kmc_hip_count_open(kmc_hip_ctx *ctx, int dev, const kmc_hip_split_params *p, kmc_hip_count **out);
+int kmc_hip_count_part(kmc_hip_ctx *ctx, kmc_hip_count *session, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint64_t *n_reads);
+int kmc_hip_count_finish(kmc_hip_ctx *ctx, kmc_hip_count *session, const kmc_hip_bin_params *bp, uint64_t stats[4], uint64_t totals[4], uint64_t *n_records);
+int kmc_hip_count_order(kmc_hip_ctx *ctx, kmc_hip_count *session, uint32_t out_lut_prefix_len, kmc_hip_db_view *view);
+int kmc_hip_count_info(kmc_hip_ctx *ctx, kmc_hip_count *session, uint64_t info[6]);
+int kmc_hip_count_timings(kmc_hip_ctx *ctx, kmc_hip_count *session, double seconds[4]);
+void kmc_hip_count_close(kmc_hip_ctx *ctx, kmc_hip_count *session);
+/* Test hook in the style of kmc_hip_debug_expand: k_cnt_gather, the segmented copy of _finish, on a table of n_segments x {source offset, destination offset, bytes}
+ * (host memory; offsets into d_src / d_dst, device memory), and the wait for it. No byte outside a destination segment is written, none outside
+ * [source, source + bytes + 16) of a segment is read. $KMC_HIP_COUNT_GATHER_WGS: workgroups of the persistent grid (default 2048). */
+int kmc_hip_debug_gather_segments(kmc_hip_ctx *ctx, int dev, const uint8_t *d_src, uint8_t *d_dst, const uint64_t *table, uint64_t n_segments);
 
 #ifdef __cplusplus
 }

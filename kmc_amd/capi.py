@@ -83,6 +83,9 @@ SPLIT_ESTIMATE = 4  # KMC_HIP_SPLIT_ESTIMATE: flags bit 2, --opt-out-size (the p
 SPLIT_COVERS_ESTIMATE = 0x102  # KMC_HIP_SPLIT_COVERS_ESTIMATE
 SPLIT_COVERS_SMALLK = 0x103  # KMC_HIP_SPLIT_COVERS_SMALLK: kmc_hip_smallk_open / _part / _read / _close (k <= 13 counted on the device)
 SMALLK_MAX_K = 13
+SPLIT_COVERS_COUNT = 0x105  # KMC_HIP_SPLIT_COVERS_COUNT: kmc_hip_count_open / _part / _finish / _order / _info / _timings / _close (a counting session; 0x104 stays unknown)
+UNCOVERED = 1  # KMC_HIP_UNCOVERED: malformed text the kernels do not reproduce; nothing was produced
+SPLIT_LINE_CAP = (65536 + 1) * 8  # the reference's mem_part_pmm_reads (kmc.h:419, splitter.cpp:18): kmc_hip_split_params.line_cap of a front end
 SPLIT_COVERS_HOMOPOLYMER = 0x100  # KMC_HIP_SPLIT_COVERS_HOMOPOLYMER: ask kmc_hip_split_covers before setting the flag (an older library ignores it)
 
 
@@ -141,6 +144,7 @@ SYMBOLS = [
     "kmc_hip_db_set_op_device", "kmc_hip_db_query_reads_device",
     "kmc_hip_db_reduce_device", "kmc_hip_db_histogram_device", "kmc_hip_db_dump_device",
     "kmc_hip_db_expr_device",
+    "kmc_hip_count_open", "kmc_hip_count_part", "kmc_hip_count_finish", "kmc_hip_count_order", "kmc_hip_count_info", "kmc_hip_count_timings", "kmc_hip_count_close", "kmc_hip_debug_gather_segments",
 ]
 
 _LIB = None
@@ -240,8 +244,26 @@ def load():
         L.kmc_hip_db_dump_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, u64p]
     if hasattr(L, "kmc_hip_db_expr_device"):  # added within ABI version 4
         L.kmc_hip_db_expr_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.POINTER(DbExprStep), C.c_uint32, C.POINTER(DbOp), vp, C.c_uint64, vp, u64p, u64p]
+    bind_count(L)
     _LIB = L
     return L
+
+
+def bind_count(L):
+    """the prototypes of the counting session and its test hook on a loaded library (added within ABI version 4: ask kmc_hip_split_covers(SPLIT_COVERS_COUNT))"""
+    if not hasattr(L, "kmc_hip_count_open"):
+        return
+    vp = C.c_void_p
+    L.kmc_hip_split_set_map.argtypes = [vp, C.c_int, vp, C.c_uint32]
+    L.kmc_hip_count_open.argtypes = [vp, C.c_int, C.POINTER(SplitParams), C.POINTER(vp)]
+    L.kmc_hip_count_part.argtypes = [vp, vp, C.c_int, C.POINTER(SplitParams), vp, C.c_uint64, u64p]
+    L.kmc_hip_count_finish.argtypes = [vp, vp, C.POINTER(BinParams), u64p, u64p, u64p]
+    L.kmc_hip_count_order.argtypes = [vp, vp, C.c_uint32, C.POINTER(DbView)]
+    L.kmc_hip_count_info.argtypes = [vp, vp, u64p]
+    L.kmc_hip_count_timings.argtypes = [vp, vp, C.POINTER(C.c_double)]
+    L.kmc_hip_count_close.argtypes = [vp, vp]
+    L.kmc_hip_count_close.restype = None
+    L.kmc_hip_debug_gather_segments.argtypes = [vp, C.c_int, vp, vp, vp, C.c_uint64]
 
 
 def _vp(a: np.ndarray):
@@ -534,6 +556,12 @@ class Context:
         self._chk(self.L.kmc_hip_db_expr_device(self.h, dev, kmer_len, va, len(views), sa, len(steps), C.byref(out), d_out, out_capacity, d_lut_out, C.byref(n), st))
         return n.value, dict(zip(DBX_STATS, (int(x) for x in st)))
 
+    def debug_gather_segments(self, d_src: int, d_dst: int, table: np.ndarray, dev: int = 0):
+        """test hook: k_cnt_gather on a table of (source offset, destination offset, bytes) triples over two device buffers"""
+        bind_count(self.L)
+        t = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, 3)
+        self._chk(self.L.kmc_hip_debug_gather_segments(self.h, dev, C.c_void_p(d_src), C.c_void_p(d_dst), _vp(t) if t.size else None, t.shape[0]))
+
     def host_alloc(self, nbytes: int) -> np.ndarray:
         """Pinned host memory as a uint8 array (free with host_free(arr))."""
         p = C.c_void_p()
@@ -551,6 +579,76 @@ class Context:
         a = np.ascontiguousarray(per_dev, dtype=np.uint64).copy()
         self._chk(self.L.kmc_hip_allreduce_stats(self.h, a.ctypes.data_as(u64p)))
         return a
+
+
+class CountSession:
+    """kmc_hip_count: a reads file part by part -> one ordered database body on the device (include/kmc_hip.h). ctx: a Context, or anything with its L, h and _chk.
+    k, signature length, number of bins and strands are fixed here; the signature map (4^m + 1 int32) is uploaded with kmc_hip_split_set_map."""
+
+    def __init__(self, ctx, k: int, signature_len: int, n_bins: int, both_strands: bool, sig_map: np.ndarray, dev: int = 0):
+        self.ctx, self.dev, self.h = ctx, dev, None
+        if not hasattr(ctx.L, "kmc_hip_count_open"):
+            raise KmcHipError(-1, f"{lib_path()} has no kmc_hip_count_open")
+        bind_count(ctx.L)
+        self.fixed = (k, signature_len, n_bins, 1 if both_strands else 0)
+        sig_map = np.ascontiguousarray(sig_map, dtype=np.int32)
+        assert sig_map.size == (1 << (2 * signature_len)) + 1
+        ctx._chk(ctx.L.kmc_hip_split_set_map(ctx.h, dev, _vp(sig_map), signature_len))
+        h = C.c_void_p()
+        ctx._chk(ctx.L.kmc_hip_count_open(ctx.h, dev, C.byref(self.split_params()), C.byref(h)))
+        self.h = h
+
+    def split_params(self, file_type: int = 1, line_cap: int = SPLIT_LINE_CAP, part_kind: int = 0, flags: int = 0, **other) -> SplitParams:
+        """the session's parameters with a part's own; **other overrides fields (tests)"""
+        k, m, n_bins, both = self.fixed
+        p = SplitParams(k, m, n_bins, 0, both, file_type, line_cap, part_kind, flags)
+        for name, v in other.items():
+            setattr(p, name, v)
+        return p
+
+    def part_rc(self, text, p: SplitParams, slot: int = 0):
+        """one part; -> (return code, reads): the code is 0, UNCOVERED or negative, nothing is raised"""
+        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        n = C.c_uint64(0)
+        rc = self.ctx.L.kmc_hip_count_part(self.ctx.h, self.h, slot, C.byref(p), _vp(t) if t.size else None, t.size, C.byref(n))
+        return rc, n.value
+
+    def part(self, text, p: SplitParams, slot: int = 0) -> int:
+        """one part; returns its reads. KMC_HIP_UNCOVERED raises like an error: the session is as it was"""
+        rc, n = self.part_rc(text, p, slot)
+        if rc == UNCOVERED:
+            raise KmcHipError(rc, "KMC_HIP_UNCOVERED: the part's text is malformed in a way the device splitter does not reproduce (blank lines, a quality line of another "
+                                  "length than its sequence, control characters)")
+        self.ctx._chk(rc)
+        return n
+
+    def finish(self, bp: BinParams):
+        """-> (stats[4] in KMC_HIP_STAT_* order, totals[4] = reads, super-k-mers, k-mers, bytes of bin records, records kept)"""
+        st, tot, n = np.zeros(4, dtype=np.uint64), np.zeros(4, dtype=np.uint64), C.c_uint64(0)
+        self.ctx._chk(self.ctx.L.kmc_hip_count_finish(self.ctx.h, self.h, C.byref(bp), st.ctypes.data_as(u64p), tot.ctypes.data_as(u64p), C.byref(n)))
+        return st, tot, n.value
+
+    def order(self, out_lut_prefix_len: int) -> DbView:
+        """the ordered body as a view; its memory is the session's and lives until the next order() or close()"""
+        v = DbView()
+        self.ctx._chk(self.ctx.L.kmc_hip_count_order(self.ctx.h, self.h, out_lut_prefix_len, C.byref(v)))
+        return v
+
+    def info(self) -> dict:
+        a = np.zeros(6, dtype=np.uint64)
+        self.ctx._chk(self.ctx.L.kmc_hip_count_info(self.ctx.h, self.h, a.ctypes.data_as(u64p)))
+        return dict(zip(("n_parts", "n_chunks", "n_segments", "n_batches", "largest_bin", "bins_in_use"), (int(x) for x in a)))
+
+    def timings(self) -> dict:
+        """seconds of the last finish() and order(): dict(layout, gather, stage2, order); gather by HIP events around k_cnt_gather, the others wall clock"""
+        t = (C.c_double * 4)()
+        self.ctx._chk(self.ctx.L.kmc_hip_count_timings(self.ctx.h, self.h, t))
+        return dict(zip(("layout", "gather", "stage2", "order"), (float(x) for x in t)))
+
+    def close(self):
+        if self.h:
+            self.ctx.L.kmc_hip_count_close(self.ctx.h, self.h)
+            self.h = None
 
 
 # ---- synthetic stage-2 inputs (libkmc_synth.so)

@@ -279,7 +279,10 @@ int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, 
 
 int kmc_hip_split_covers(uint32_t what)
 {
-	return what <= 2 || what == 4 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER || what == KMC_HIP_SPLIT_COVERS_ESTIMATE || what == KMC_HIP_SPLIT_COVERS_SMALLK ? 1 : 0;
+	return what <= 2 || what == 4 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER || what == KMC_HIP_SPLIT_COVERS_ESTIMATE || what == KMC_HIP_SPLIT_COVERS_SMALLK ||
+	               what == KMC_HIP_SPLIT_COVERS_COUNT
+	           ? 1
+	           : 0;
 }
 
 /* ---- histogram estimation while counting (--opt-out-size): the device's share of the reference's CntHashEstimator counters ---- */

@@ -159,11 +159,15 @@ int kmc_hip_init(const int *device_ids, int n_dev, kmc_hip_ctx **out)
 }
 
 static void hb_report();
+namespace {
+void count_close_all(kmc_hip_ctx *ctx); /* host_count.hip.h */
+}
 void kmc_hip_destroy(kmc_hip_ctx *ctx)
 {
 	if (!ctx)
 		return;
 	hb_report();
+	count_close_all(ctx); /* hipFree waits for the device */
 	for (auto &d : ctx->devs) {
 		(void)hipSetDevice(d->ordinal);
 		(void)hipDeviceSynchronize();

@@ -32,6 +32,7 @@
 #include "arena_sort.hip.h"
 #include "order_db.hip.h"
 #include "stage1_kernels.hip.h"
+#include "count_gather.hip.h"
 
 namespace {
 
@@ -288,6 +289,7 @@ struct kmc_hip_ctx {
 	bool comms_ready = false;
 	u64 portion = PORTION_MAX;
 	std::mutex mtx;
+	std::vector<struct kmc_hip_count *> counts; /* open counting sessions (host_count.hip.h): kmc_hip_destroy closes them */
 };
 
 namespace {
@@ -591,6 +593,7 @@ struct DevTemps {
 #include "host_multi_device_bin.hip.h" /* one bin over all devices of the context */
 #include "host_cabi_stage2.hip.h" /* the C-ABI of stage 2: lifetime, narrow boundary, full boundary (one bin / several bins per call, device-resident batches) */
 #include "host_cabi_stage1.hip.h" /* the C-ABI test hooks and stage 1 on the device (reads -> bins in HBM; one part of input text -> bin records) */
+#include "host_count.hip.h" /* the counting session: parts of a reads file -> bin records kept in HBM -> gathered bins -> stage 2 -> one ordered database body */
 #include "host_cabi_collective.hip.h" /* the tally all-reduce over the devices of a context (RCCL) and the instrumentation entries */
 #include "host_setops.hip.h" /* set operations between two ordered databases (`kmc_tools simple`) */
 #include "host_query.hip.h" /* the reads of a file against an ordered database (`kmc_tools filter`) */

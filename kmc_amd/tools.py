@@ -883,8 +883,189 @@ def complex(argv, ctx=None) -> dict:  # noqa: A001 (the mode's name)
     return st
 
 
+COUNT_USAGE = """usage: python -m kmc_amd.tools count [options] <input_file | @file_of_inputs> <out> [<working_dir>]
+  the argument order of `kmc`, so a kmc command line carries over. Read: -k<len> (25; 14..224) -ci<v> (2) -cx<v> (1e9) -cs<v> (255) -b -fa | -fq (default) | -fm -hc
+  -p<signature_len> (min(9, k); 5..11) -n<bins> (512; at most 2048). Accepted and ignored (they size the reference's host pipeline): -t* -m* -r -sf* -sp* -sr* -v and
+  <working_dir>. Everything else is refused. Writes <out>.kmc_pre / .kmc_suf as `kmc` followed by `kmc_tools transform <db> sort <out>` does."""
+COUNT_PART_BYTES = 32 << 20
+COUNT_MAP_MULTIPLIER = 0x9E3779B1
+_COUNT_REFUSED = {"-okff": "KFF output", "-e": "the k-mer number estimation alone", "--opt-out-size": "the output size optimisation", "-fbam": "BAM input (the session entry takes BAM parts; "
+                  "this front end does not read BGZF)", "-fkmc": "KMC-database input", "-sm": "strict memory mode", "-j": "the JSON summary", "-w": "a run without output"}
+
+
+def parse_count(argv) -> dict:
+    """-> dict(k, ci, cx, cs, both, file_type (0 FASTA, 1 FASTQ, 2 multi-line FASTA), hc, m, n_bins, inputs, out)"""
+    o = dict(k=25, ci=2, cx=10**9, cs=255, both=True, file_type=1, hc=False, m=None, n_bins=512)
+    pos = []
+    for a in argv:
+        if not a.startswith("-") or a == "-":
+            pos.append(a)
+        elif a.startswith(("-t", "-m", "-sf", "-sp", "-sr")) and not a.startswith("-sm") or a in ("-r", "-v"):
+            continue  # threads, memory, RAM-only mode, the splitters / readers / sorters, verbosity: they size the reference's host pipeline
+        elif a.startswith("-ci"):
+            o["ci"] = _num(a, a[:3])
+        elif a.startswith("-cx"):
+            o["cx"] = _num(a, a[:3])
+        elif a.startswith("-cs"):
+            o["cs"] = _num(a, a[:3])
+        elif a.startswith("-k"):
+            o["k"] = _num(a, a[:2])
+        elif a.startswith("-p"):
+            o["m"] = _num(a, a[:2])
+        elif a.startswith("-n"):
+            o["n_bins"] = _num(a, a[:2])
+        elif a == "-b":
+            o["both"] = False
+        elif a == "-hc":
+            o["hc"] = True
+        elif a in ("-fa", "-fq", "-fm"):
+            o["file_type"] = {"-fa": 0, "-fq": 1, "-fm": 2}[a]
+        else:
+            why = next((w for pre, w in _COUNT_REFUSED.items() if a.startswith(pre)), None)
+            raise UsageError(f"count: option {a} is not read" + (f" ({why})" if why else "") + "\n" + COUNT_USAGE)
+    if len(pos) not in (2, 3):
+        raise UsageError(COUNT_USAGE)
+    k = o["k"]
+    if k < 14:
+        raise UsageError(f"count: -k{k}: k <= 13 is counted without bins, by the small-k entries of the library (kmc_hip_smallk_open / _part / _read); this front end takes k 14..224")
+    if k > 224:
+        raise UsageError(f"count: -k{k}: at most 224 (the ordered database's record width)")
+    if o["m"] is None:
+        o["m"] = min(9, k)
+    if not 5 <= o["m"] <= 11:
+        raise UsageError(f"count: -p{o['m']}: the signature length is 5..11")
+    if not 1 <= o["n_bins"] <= 2048:
+        raise UsageError(f"count: -n{o['n_bins']}: 1..2048 bins")
+    if o["ci"] < 1 or o["cs"] < 1 or o["cx"] < o["ci"]:
+        raise UsageError("count: -ci and -cs are at least 1, -cx at least -ci")
+    if pos[0].startswith("@"):
+        try:
+            with open(pos[0][1:]) as f:
+                o["inputs"] = [ln.strip() for ln in f if ln.strip()]
+        except OSError as e:
+            raise UsageError(f"cannot open file: {pos[0][1:]} ({e.strerror})")
+    else:
+        o["inputs"] = [pos[0]]
+    o["out"] = pos[1]
+    return o
+
+
+def count_signature_map(signature_len: int, n_bins: int, multiplier: int = COUNT_MAP_MULTIPLIER) -> np.ndarray:
+    """The signature -> bin map of `count`, int32[4^m + 1] (the last entry is the special signature's): bin = ((sig * multiplier mod 2^32) >> 8) % n_bins, a fixed
+    pseudo-random spread. It does not reproduce CSignatureMapper's balancing from stage-0 statistics; the database does not depend on the map (all occurrences of a
+    k-mer share one signature), only the balance of the bins does, which the run reports."""
+    sig = np.arange((1 << (2 * signature_len)) + 1, dtype=np.uint64)
+    return ((((sig * np.uint64(multiplier)) & np.uint64(0xFFFFFFFF)) >> np.uint64(8)) % np.uint64(n_bins)).astype(np.int32)
+
+
+def multiline_parts(path: str, part_bytes: int):
+    """A multi-line FASTA file in parts as the reference's reader hands them to the splitter (CFastqReader::GetPartFromMultilneFasta, fastq_reader.cpp:399-468): a title
+    keeps its line end, the sequence lines lose theirs. Parts are cut in front of a '>' at a line start; a record longer than part_bytes makes its part longer."""
+    import gzip
+
+    def strip(buf):
+        if not buf.size:
+            return buf
+        start, _, end = readsio.line_table(buf) if buf[-1] == 10 else readsio.line_table(np.concatenate([buf, [10]]).astype(np.uint8))
+        keep = (buf != 10) & (buf != 13)
+        for s, e in zip(start[buf[start] == 62], end[buf[start] == 62]):  # titles are few: one per sequence
+            keep[s:min(e, buf.size)] = True
+        return buf[keep]
+
+    held, last = [], 10  # the chunks of the part that is growing (joined once, when a cut is found: a sequence far longer than a part costs one copy), the byte before the next chunk
+    with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
+        while True:
+            chunk = f.read(part_bytes)
+            if not chunk:
+                break
+            c = np.frombuffer(chunk, dtype=np.uint8)
+            at = np.flatnonzero((c[1:] == 62) & (c[:-1] == 10)) + 1  # a '>' at a line start
+            n = int(at[-1]) if at.size else (0 if held and last == 10 and c[0] == 62 else -1)
+            last = int(c[-1])
+            if n < 0 or (n == 0 and not held):
+                held.append(c)
+                continue
+            buf = np.concatenate(held + [c[:n]]) if held or n < c.size else c
+            if buf.size:
+                yield strip(buf)
+            held = [c[n:]]
+    rest = np.concatenate(held) if held else np.zeros(0, dtype=np.uint8)
+    if rest.size:
+        yield strip(rest)
+
+
+def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_MULTIPLIER):
+    """`kmc` + `kmc_tools transform sort` on the device: the reads of the input files go through a counting session (capi.CountSession) part by part, the ordered body is
+    written as a KMC1 database. Returns dict(stats = the four tallies of stage 2 by name, totals = reads, super-k-mers, k-mers, bytes of bin records, n_records, n_parts,
+    n_segments, n_batches, balance = k-mers of the largest bin / of the mean bin); keep=True: (that dict, the open session, its view) — the caller goes on on the device and closes the session."""
+    o = parse_count(argv)
+    if part_bytes is None:
+        part_bytes = int(os.environ.get("KMC_HIP_COUNT_PART_MB", "0")) << 20 or COUNT_PART_BYTES
+    k = o["k"]
+    own = ctx is None
+    if own:
+        ctx = capi.Context((0,))
+    ses = None
+    try:
+        ses = capi.CountSession(ctx, k, o["m"], o["n_bins"], o["both"], count_signature_map(o["m"], o["n_bins"], map_multiplier))
+        p = ses.split_params(file_type=o["file_type"], flags=capi.SPLIT_HOMOPOLYMER if o["hc"] else 0)
+        n_parts = 0
+        for path in o["inputs"]:
+            try:
+                for i, part in enumerate(multiline_parts(path, part_bytes) if o["file_type"] == 2 else readsio.parts(path, o["file_type"] == 1, part_bytes)):
+                    try:
+                        ses.part(part, p)
+                    except capi.KmcHipError as e:
+                        if e.code == capi.UNCOVERED:
+                            raise UsageError(f"count: {path}, part {i}: {e}")
+                        raise
+                    n_parts += 1
+            except OSError as e:
+                raise UsageError(f"cannot open file: {path} ({e.strerror})")
+            except readsio.FormatError as e:
+                raise UsageError(f"count: {path}: {e}")
+        # the bins' own prefix length: invisible in the result; the shortest one keeps their LUTs small
+        p_bins = next(q for q in range(1, 5) if (k - q) % 4 == 0)
+        bp = capi.make_params(k, both_strands=1 if o["both"] else 0, cutoff_min=o["ci"], cutoff_max=o["cx"], counter_max=o["cs"], lut_prefix_len=p_bins)
+        st, tot, n_records = ses.finish(bp)
+        info = ses.info()
+        p_out = dbio.best_lut_prefix_len(k, n_records)
+        view = ses.order(p_out)
+        rb = (k - p_out) // 4 + view.counter_size
+        recs, lut = np.zeros(n_records * rb, dtype=np.uint8), np.zeros(1 << (2 * p_out), dtype=np.uint64)
+        if n_records:
+            ctx.d2h(recs, view.d_recs)
+        ctx.d2h(lut, view.d_lut)
+        dbio.write_kmc1(o["out"], k, view.counter_size, p_out, o["ci"], o["cx"], o["both"], lut, recs)
+        res = dict(stats=dict(zip(("n_unique", "n_below_min", "n_above_max", "n_total"), (int(x) for x in st))),
+                   totals=dict(zip(("n_reads", "n_superkmers", "n_kmers", "bin_bytes"), (int(x) for x in tot))), n_records=n_records, n_parts=n_parts,
+                   n_segments=info["n_segments"], n_batches=info["n_batches"], balance=info["largest_bin"] * o["n_bins"] / max(int(tot[2]), 1))
+        if keep:
+            ses_kept, ses = ses, None
+            return res, ses_kept, view
+        return res
+    finally:
+        if ses is not None:
+            ses.close()
+        if own and not (keep and ses is None):
+            ctx.close()
+
+
+def count_report(res: dict) -> str:
+    """the lines of `kmc`'s summary (kmc_CLI/kmc.cpp:410-419) + the bins' balance"""
+    s, t = res["stats"], res["totals"]
+    rows = [("No. of k-mers below min. threshold", s["n_below_min"]), ("No. of k-mers above max. threshold", s["n_above_max"]), ("No. of unique k-mers", s["n_unique"]),
+            ("No. of unique counted k-mers", s["n_unique"] - s["n_below_min"] - s["n_above_max"]), ("Total no. of k-mers", s["n_total"]), ("Total no. of reads", t["n_reads"]),
+            ("Total no. of super-k-mers", t["n_superkmers"])]
+    return "\n".join("   %-35s: %12d" % r for r in rows) + "\n   %-35s: %12.2f  (%d parts, %d segments gathered, %d stage-2 batches)" % (
+        "Largest bin / mean bin (k-mers)", res["balance"], res["n_parts"], res["n_segments"], res["n_batches"])
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
+    if argv and argv[0] == "count":
+        print(count_report(count(argv[1:])))
+        return 0
     if argv and argv[0] == "filter":
         print(", ".join(f"{a} {b}" for a, b in filter_reads(argv[1:]).items()))
         return 0
@@ -902,7 +1083,7 @@ def main(argv=None) -> int:
         return 0
     if not argv or argv[0] != "simple":
         raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...\n" + FILTER_USAGE + "\n" + TRANSFORM_USAGE + "\n"
-                         + COMPLEX_USAGE)
+                         + COMPLEX_USAGE + "\n" + COUNT_USAGE)
     for (o, st) in zip(parse_simple(argv[1:])[1], simple(argv[1:])):
         print(f"{o['op']} -> {o['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
     return 0
