@@ -343,27 +343,21 @@ int kmc_hip_sort_records(kmc_hip_ctx *ctx, int dev, void *recs, uint64_t n, uint
 }
 
 /* ---- full boundary ---- */
-static int process_bin_device_on(kmc_hip_ctx *ctx, int dev, Slot &s, const DevParams &P, u64 lut_entries, const uint8_t *d_superkmers,
-                                 uint64_t size, uint64_t n_rec, const uint64_t *d_pack_start, uint64_t n_packs, uint8_t *d_out,
-                                 uint64_t out_capacity, uint64_t *d_out_bytes, uint64_t *d_lut, uint64_t *d_stats, int sync)
+static int process_bin_device_on(Slot &s, const DevParams &P, u64 lut_entries, const kmc_hip_bin_desc &b, int sync)
 {
-	(void)ctx;
-	(void)dev;
 	std::lock_guard<std::mutex> lck(s.mtx);
 	s.timed = sync || (s.async_seq++ % TIMING_SAMPLE) == 0; /* async_seq restarts with kmc_hip_scatter_totals(reset) */
-	if (int rc = run_bin_device(s, P, d_superkmers, size, n_rec, (const u64 *)d_pack_start, n_packs, d_out, out_capacity, (u64 *)d_out_bytes,
-	                            (u64 *)d_lut, lut_entries, (u64 *)d_stats, false, !sync))
+	if (int rc = run_bin_device(s, P, b, lut_entries, false, !sync))
 		return rc;
 	if (!sync)
 		return 0;
 	HIPCHK(hipStreamSynchronize(s.stream));
 	bool redo = false;
-	if (n_rec >= 2)
+	if (b.n_rec >= 2)
 		if (int rc = read_redo(s, redo))
 			return rc;
 	if (redo) {
-		if (int rc = run_bin_device(s, P, d_superkmers, size, n_rec, (const u64 *)d_pack_start, n_packs, d_out, out_capacity, (u64 *)d_out_bytes,
-		                            (u64 *)d_lut, lut_entries, (u64 *)d_stats, true))
+		if (int rc = run_bin_device(s, P, b, lut_entries, true))
 			return rc;
 		HIPCHK(hipStreamSynchronize(s.stream));
 	}
@@ -394,8 +388,8 @@ int kmc_hip_process_bin_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_para
 		si = (int)(d.rr++ % N_BATCH_STREAMS);
 	}
 	const u64 lut_entries = P.kff ? 0 : kmc_hip_lut_entries(params);
-	return process_bin_device_on(ctx, dev, d.slot[si], P, lut_entries, d_superkmers, size, n_rec, d_pack_start, n_packs, d_out, out_capacity,
-	                             d_out_bytes, d_lut, d_stats, sync);
+	const kmc_hip_bin_desc b = {d_superkmers, size, n_rec, d_pack_start, n_packs, d_out, out_capacity, d_out_bytes, d_lut, d_stats};
+	return process_bin_device_on(d.slot[si], P, lut_entries, b, sync);
 }
 
 int kmc_hip_process_bins_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_params *params, const kmc_hip_bin_desc *bins, uint64_t n_bins,
@@ -444,11 +438,9 @@ int kmc_hip_process_bins_device(kmc_hip_ctx *ctx, int dev, const kmc_hip_bin_par
 		u64 grp_recs = 0;
 		auto flush = [&]() -> int {
 			int rc = 0;
-			if (grp.size() == 1) {
-				const kmc_hip_bin_desc &b = *grp[0];
-				rc = process_bin_device_on(ctx, dev, d.slot[t], P, lut_entries, b.d_superkmers, b.size, b.n_rec, b.d_pack_start, b.n_packs, b.d_out, b.out_capacity,
-				                           b.d_out_bytes, b.d_lut, b.d_stats, 0);
-			} else if (grp.size() > 1) {
+			if (grp.size() == 1)
+				rc = process_bin_device_on(d.slot[t], P, lut_entries, *grp[0], 0);
+			else if (grp.size() > 1) {
 				Slot &sl = d.slot[t];
 				std::lock_guard<std::mutex> lck(sl.mtx);
 				sl.timed = (sl.async_seq++ % TIMING_SAMPLE) == 0;

@@ -1,4 +1,4 @@
-/* kmc_amd/csrc/host_plan_and_groups.hip.h — part of kmc_hip.hip (included there, not compiled on its own): the sort planner, the HBM passes, the groups of bins (front end, LSD / bucket-count / rank finishers), the redo of flagged groups. */
+/* kmc_amd/csrc/host_plan_and_groups.hip.h — part of kmc_hip.hip (included there, not compiled on its own): the sort planner, the HBM passes, the groups of bins (front end, the tail both finishers share, LSD / rank finishers, the arena's plan and launches), the redo of flagged groups. */
 /* ---- zero-region planning --------------------------------------------------------------------------------------- */
 /* Small LUTs are sharded: in sorted order every tile in flight updates the same one or two entries, and same-address device atomics
  * serialise (r01: 11 of the compaction's 12 ms at 64 entries). From 4^6 entries on the tiles in flight spread over enough of them.
@@ -46,30 +46,25 @@ int hybrid_mode()
 	const int o = g_hybrid_override.load(std::memory_order_relaxed);
 	if (o != INT32_MIN)
 		return o;
-	static const int v = [] {
-		/* 0 = LSD passes over every byte + k_compact (rounds 1-2); 1 = default: the top key bytes through HBM passes, every bucket-aligned tile ranked and
-		 * counted inside LDS by k_bucket_rank (round 4: every record width; KMC_HIP_RANK_FUSE=0: one-word records ranked in place + k_compact, wider ones LSD);
-		 * -h = force `h` top bytes (tuning). (2 — round 3's k_bucket_count / k_bucket_sort — left the library in round 6 and is taken as 1.) */
-		const char *e = getenv("KMC_HIP_HYBRID");
-		const int m = e ? atoi(e) : 1;
-		return m >= 2 ? 1 : m;
-	}();
+	/* 0 = LSD passes over every byte + k_compact (rounds 1-2); 1 = default: the top key bytes through HBM passes, every bucket-aligned tile ranked and
+	 * counted inside LDS by k_bucket_rank (round 4: every record width; KMC_HIP_RANK_FUSE=0: one-word records ranked in place + k_compact, wider ones LSD);
+	 * -h = force `h` top bytes (tuning). (2 — round 3's k_bucket_count / k_bucket_sort — left the library in round 6 and is taken as 1.) */
+	static const int v = std::min(env_int("KMC_HIP_HYBRID", 1), 1);
 	return v;
 }
 bool arena_enabled()
 {
-	static const bool v = [] {
-		const char *e = getenv("KMC_HIP_ARENA"); /* 0 (A/B runs): round 5's finisher — big buckets walked by the whole workgroup, k_giant_tiles, bins with a satellite redone */
-		return !e || atoi(e) != 0;
-	}();
+	static const bool v = env_on("KMC_HIP_ARENA"); /* 0 (A/B runs): round 5's finisher — big buckets walked by the whole workgroup, k_giant_tiles, bins with a satellite redone */
 	return v;
 }
 bool rank_enabled()
 {
-	static const bool v = [] {
-		const char *e = getenv("KMC_HIP_RANK"); /* 0: groups of one-word records keep the LSD passes over every byte */
-		return !e || atoi(e) != 0;
-	}();
+	static const bool v = env_on("KMC_HIP_RANK"); /* 0: groups of one-word records keep the LSD passes over every byte */
+	return v;
+}
+bool two_phase_enabled()
+{
+	static const bool v = env_on("KMC_HIP_TWO_PHASE"); /* 0 = always the look-back (k_compact), no tile counted where it lies (k_bucket_rank) */
 	return v;
 }
 template <int SIZE>
@@ -113,10 +108,7 @@ SortPlan plan_sort(u64 n, u32 key_bytes, u32 key_bits, bool classic, bool rank =
 		sp.top = key_bytes;
 	/* (no finer buckets after a redo since round 4: a tile with a bucket beyond LDS goes to k_giant_tiles / the arena, and what still comes back is ONE k-mer repeated a
 	 * million times — no number of passes splits that; a fifth pass would only cost every later group its time, and records of two words and more their indirect sort) */
-	static const int forced = [] {
-		const char *e = getenv("KMC_HIP_RANK_TOP"); /* tuning: this many top bytes through HBM */
-		return e ? atoi(e) : 0;
-	}();
+	static const int forced = env_int("KMC_HIP_RANK_TOP", 0); /* tuning: this many top bytes through HBM */
 	if (forced >= 1 && (u32)forced + 1 <= key_bytes && 8 * (u32)forced > spare)
 		sp.top = (u32)forced;
 	if (sp.local() && sp.top >= 1 && key_bits - sp.hbits() <= rem_limit && sp.hbits() <= 48)
@@ -234,11 +226,7 @@ int sort_device_t(Slot &s, const ZeroPlan &z, u64 *d_recs, u64 *d_tmp, u64 n, co
 				}
 				/* experiment (round 6): dynamic LDS beyond what the kernel uses = ONE scatter workgroup per CU instead of two, so that with several groups in
 				 * flight a finisher workgroup (12 waves, 72 KB) of another group fits beside it (16 waves, 59 + 24 KB) */
-				static const size_t scatter_pad = [] {
-					const char *e = getenv("KMC_HIP_SCATTER_LDS_PAD");
-					const size_t v = e ? (size_t)strtoull(e, nullptr, 10) : (size_t)0;
-					return v > 32 * 1024 ? (size_t)32 * 1024 : v;
-				}();
+				static const size_t scatter_pad = (size_t)env_count("KMC_HIP_SCATTER_LDS_PAD", 0, 32 * 1024);
 				k_onesweep<SIZE><<<dim3((tiles + RS_TPB - 1) / RS_TPB), dim3(RS_BLOCK), rs_lds_bytes<SIZE>() + scatter_pad, s.stream>>>(
 				    src + start * SIZE, dst, cnt, pass_lo + pass, base_in, base_out, status, counters + counter_idx, tiles, err);
 				if (s.timed)
@@ -399,8 +387,63 @@ int front_end_group(Slot &s, const std::vector<BinPlan> &bins, size_t off_ghist,
 	return 0;
 }
 
-/* ---- compaction of a group (one ticket space over the tiles of all bins, each bin on its slice of the sorted array) + the fold of tally /
- * LUT shards (one small workgroup per bin) ---- */
+/* ---- the tail both finishers share: the LUT's shape, where each bin's LUT entries, tallies and tile counts go, and the two launches behind the finisher — the fold of
+ * tally / LUT shards (one small workgroup per bin) and the gather of the two-phase output. One per group, on the stack like the Grp* structs it fills. ---- */
+struct BinTail {
+	u64 *lut_base, *tally, *status; /* what the finisher itself needs of a bin */
+};
+struct GroupTail {
+	Slot &s;
+	const DevParams &P;
+	const u64 lut_entries;
+	const bool use_lut;
+	const u32 n_sh, rec_bytes, lut_mask;
+	GrpFold gf = {};
+	GrpGather gg = {};
+	GroupTail(Slot &s_, const DevParams &P_, u64 lut_entries_)
+	    : s(s_), P(P_), lut_entries(lut_entries_), use_lut(lut_entries_ && !P_.without_output && !P_.kff), n_sh(use_lut ? lut_shards_for(lut_entries_) : 1u),
+	      rec_bytes(P_.sbytes + P_.cbytes), lut_mask(P_.lut_prefix_len ? (u32)((1ull << (2 * P_.lut_prefix_len)) - 1) : 0u)
+	{
+	}
+	/* bin i of the group. `first_tile`, `n_tiles`: its output tiles among the group's; `scratch`: its slice of the free record array (NULL: no two-phase output);
+	 * `src_rec`: NULL, or the first record of every tile (GrpGather) */
+	int add_bin(size_t i, const BinPlan &b, u64 first_tile, u64 n_tiles, uint8_t *scratch, const u64 *src_rec, BinTail &bt)
+	{
+		bt.lut_base = b.d_lut;
+		if (use_lut && n_sh > 1)
+			bt.lut_base = zero_ptr<u64>(s, b.off_lutsh); /* zeroed with the rest of the zero region */
+		else if (lut_entries && !P.kff && b.d_lut) /* also without output: the caller's LUT is zero-filled by the callee (include/kmc_hip.h) */
+			HIPCHK(hipMemsetAsync(b.d_lut, 0, lut_entries * 8, s.stream));
+		gf.tally[i] = bt.tally = zero_ptr<u64>(s, b.off_tally);
+		gg.prefix[i] = gf.status[i] = bt.status = zero_ptr<u64>(s, b.off_cp_status);
+		gf.n[i] = b.n_rec;
+		gf.stats[i] = b.d_stats;
+		gf.lut_base[i] = bt.lut_base;
+		gf.lut_out[i] = b.d_lut;
+		gf.n_tiles[i] = (u32)n_tiles;
+		gf.out_bytes[i] = b.d_out_bytes;
+		gf.out_capacity[i] = gg.out_capacity[i] = b.out_capacity;
+		gg.tile_prefix[i] = (u32)first_tile;
+		gg.scratch[i] = scratch;
+		gg.out[i] = b.d_out;
+		gg.src_rec[i] = src_rec;
+		return 0;
+	}
+	/* behind the finisher of `g` bins with `tiles` output tiles. `two_phase`: the status words are tile counts, the fold turns them into prefixes and out_bytes;
+	 * `gather`: the tiles' records move from the free array (tile t at t x tile_pitch, or at src_rec[t] x tile_pitch) to the output */
+	int fold_and_gather(u32 g, u64 tiles, bool two_phase, bool gather, u64 tile_pitch)
+	{
+		gg.g = g;
+		gg.tile_prefix[g] = (u32)tiles;
+		k_compact_fold<<<dim3(g), dim3(256), 0, s.stream>>>(gf, n_sh, lut_entries, two_phase ? 1u : 0u, rec_bytes, err_ptr(s));
+		if (gather)
+			k_compact_gather<<<dim3((u32)((tiles + 3) / 4)), dim3(256), 0, s.stream>>>(gg, rec_bytes, tile_pitch);
+		HIPCHK(hipGetLastError());
+		return 0;
+	}
+};
+
+/* ---- compaction of a group (one ticket space over the tiles of all bins, each bin on its slice of the sorted array), then the tail ---- */
 /* `scratch`: the record array the sort left free (same layout as `sorted`), or NULL. With it, and when a tile's span of it is certain to hold
  * the tile's counted records — at most TILE / cutoff_min + 1 of them — the output is written in two phases (kernels.hip.h k_compact two_phase):
  * no tile waits for its offset. */
@@ -409,83 +452,133 @@ int compact_group(Slot &s, const std::vector<BinPlan> &bins, const u64 *sorted, 
 {
 	if (bins.empty())
 		return 0;
-	u32 *err = err_ptr(s);
-	u32 *counters = small_ptr<u32>(s, SM_COUNTERS);
 	if (counter_idx >= N_COUNTERS)
 		return fail(KMC_HIP_EINVAL, "too many launches for one bin");
-	const bool use_lut = lut_entries && !P.without_output && !P.kff;
-	const u32 n_sh = !use_lut ? 1u : lut_shards_for(lut_entries);
-	const u32 rec_bytes = P.sbytes + P.cbytes;
+	GroupTail tail(s, P, lut_entries);
 	const u64 tile_pitch = (u64)CpCfg<SIZE>::TILE * SIZE * 8;
-	static const bool allow_two_phase = [] {
-		const char *e = getenv("KMC_HIP_TWO_PHASE"); /* 0 = always the look-back */
-		return !e || atoi(e) != 0;
-	}();
-	const bool two_phase = allow_two_phase && scratch && !P.without_output &&
-	                       ((u64)CpCfg<SIZE>::TILE / std::max<u32>(P.cutoff_min, 1) + 1) * rec_bytes <= tile_pitch;
+	const bool two_phase = two_phase_enabled() && scratch && !P.without_output &&
+	                       ((u64)CpCfg<SIZE>::TILE / std::max<u32>(P.cutoff_min, 1) + 1) * tail.rec_bytes <= tile_pitch;
 	GrpCompact gc = {};
-	GrpFold gf = {};
-	GrpGather gg = {};
-	gc.g = gg.g = (u32)bins.size();
+	gc.g = (u32)bins.size();
 	u64 tiles = 0;
 	for (size_t i = 0; i < bins.size(); ++i) {
 		const BinPlan &b = bins[i];
-		gc.tile_prefix[i] = gg.tile_prefix[i] = (u32)tiles;
 		const u64 bin_tiles = (b.n_rec + CpCfg<SIZE>::TILE - 1) / CpCfg<SIZE>::TILE;
-		tiles += bin_tiles;
-		if (tiles > 0x7FFFFFFFull)
+		if (tiles + bin_tiles > 0x7FFFFFFFull)
 			return fail(KMC_HIP_EINVAL, "bin too large");
-		u64 *lut_base = b.d_lut;
-		if (use_lut && n_sh > 1)
-			lut_base = zero_ptr<u64>(s, b.off_lutsh); /* zeroed with the rest of the zero region */
-		else if (lut_entries && !P.kff && b.d_lut) /* also without output: the caller's LUT is zero-filled by the callee (include/kmc_hip.h) */
-			HIPCHK(hipMemsetAsync(b.d_lut, 0, lut_entries * 8, s.stream));
+		BinTail bt;
+		gc.scratch[i] = two_phase ? (uint8_t *)(scratch + b.rec_off * SIZE) : nullptr;
+		if (int rc = tail.add_bin(i, b, tiles, bin_tiles, gc.scratch[i], nullptr, bt))
+			return rc;
+		gc.tile_prefix[i] = (u32)tiles;
 		gc.S[i] = sorted + b.rec_off * SIZE;
-		gc.n[i] = gf.n[i] = b.n_rec;
+		gc.n[i] = b.n_rec;
 		gc.out[i] = b.d_out;
 		gc.out_capacity[i] = b.out_capacity;
-		gc.lut_base[i] = lut_base;
-		gc.tally[i] = zero_ptr<u64>(s, b.off_tally);
+		gc.lut_base[i] = bt.lut_base;
+		gc.tally[i] = bt.tally;
 		gc.out_bytes[i] = b.d_out_bytes;
-		gc.status[i] = zero_ptr<u64>(s, b.off_cp_status);
-		gf.tally[i] = gc.tally[i];
-		gf.stats[i] = b.d_stats;
-		gf.lut_base[i] = lut_base;
-		gf.lut_out[i] = b.d_lut;
-		gc.scratch[i] = two_phase ? (uint8_t *)(scratch + b.rec_off * SIZE) : nullptr;
-		gf.status[i] = gc.status[i];
-		gf.n_tiles[i] = (u32)bin_tiles;
-		gf.out_bytes[i] = b.d_out_bytes;
-		gf.out_capacity[i] = b.out_capacity;
-		gg.scratch[i] = gc.scratch[i];
-		gg.prefix[i] = gc.status[i];
-		gg.out[i] = b.d_out;
-		gg.out_capacity[i] = b.out_capacity;
+		gc.status[i] = bt.status;
+		tiles += bin_tiles;
 	}
-	gc.tile_prefix[bins.size()] = gg.tile_prefix[bins.size()] = (u32)tiles;
-	k_compact<SIZE><<<dim3((u32)tiles), dim3(CP_BLOCK), 0, s.stream>>>(gc, P, n_sh, lut_entries, counters + counter_idx, err,
-	                                                                   P.lut_prefix_len ? (u32)((1ull << (2 * P.lut_prefix_len)) - 1) : 0u, two_phase ? 1u : 0u);
+	gc.tile_prefix[bins.size()] = (u32)tiles;
+	k_compact<SIZE><<<dim3((u32)tiles), dim3(CP_BLOCK), 0, s.stream>>>(gc, P, tail.n_sh, lut_entries, small_ptr<u32>(s, SM_COUNTERS) + counter_idx, err_ptr(s), tail.lut_mask, two_phase ? 1u : 0u);
 	counter_idx += 1;
-	k_compact_fold<<<dim3((u32)bins.size()), dim3(256), 0, s.stream>>>(gf, use_lut ? n_sh : 1u, lut_entries, two_phase ? 1u : 0u, rec_bytes, err);
-	if (two_phase)
-		k_compact_gather<<<dim3((u32)((tiles + 3) / 4)), dim3(256), 0, s.stream>>>(gg, rec_bytes, tile_pitch);
-	HIPCHK(hipGetLastError());
-	return 0;
+	return tail.fold_and_gather(gc.g, tiles, two_phase, two_phase, tile_pitch);
 }
 
 /* ---- may a tile be counted where it lies (k_bucket_rank fused)? A tile's (suffix, counter) records go to the tile's span of the free record array; then the fold and
  * the gather of the two-phase output as after k_compact. ---- */
 template <int SIZE> bool count_applicable(const DevParams &P)
 {
-	static const bool allow_two_phase = [] {
-		const char *e = getenv("KMC_HIP_TWO_PHASE");
-		return !e || atoi(e) != 0;
-	}();
 	/* a tile of L records counts at most L / cutoff_min k-mers, and its span of the free array has 8 SIZE bytes per record (+ 3 bytes of dword padding,
 	 * inside the span as long as a stored record is not longer than that) */
-	const u32 rec_bytes = P.sbytes + P.cbytes;
-	return allow_two_phase && (P.without_output || rec_bytes <= (u32)(SIZE * 8));
+	return two_phase_enabled() && (P.without_output || P.sbytes + P.cbytes <= (u32)(SIZE * 8));
 }
+
+/* ---- the arena (one-word records, arena_sort.hip.h): the buckets beyond BR_MID records of a group, sorted together by HBM passes of their own ---- */
+/* Every bucket beyond BR_MID records is disjoint from every other, a giant one owns a tile — n_total / BR_MID + wins entries can never be exceeded. Work area:
+ * entries | arena_off | item_off | bucket numbers | digit bases | look-back rows of up to AR_MAX_PASS passes over up to n_total records. Fills `aw` and gr.arena_*. */
+int plan_arena(Slot &s, GrpRank &gr, ArenaWork &aw, u32 &ar_pass_max, u32 *d_arena, u32 rbits, u64 wins, u64 n_total)
+{
+	/* tests: a list too short for the group's buckets — the plan is dropped, the group comes back through LSD passes */
+	static const u64 cap_limit = env_count("KMC_HIP_ARENA_CAP", ~0ull);
+	const u64 cap = std::min<u64>(n_total / BR_MID + wins + 16, cap_limit);
+	const u64 max_tiles = (std::min<u64>(n_total, AR_MAX_RECORDS) + RsCfg<1>::TILE - 1) / RsCfg<1>::TILE;
+	u32 obits = 0;
+	while (obits < 32 && (1ull << obits) < cap)
+		++obits;
+	ar_pass_max = std::min<u32>(AR_MAX_PASS, (rbits + obits + 7) / 8);
+	size_t off = 0;
+	auto take = [&off](size_t bytes) {
+		const size_t at = off;
+		off += bytes;
+		return at;
+	};
+	const size_t o_ent = take(up256(cap * sizeof(ArenaEntry))), o_aoff = take(up256((cap + 1) * 4)), o_ioff = take(up256((cap + 1) * 4)), o_hi = take(up256(cap * 8));
+	const size_t o_dbase = take(up256((size_t)(AR_MAX_PASS + 1) * 256 * 8)), stride = up256(max_tiles * 256 * 4), o_status = take(stride * ar_pass_max);
+	int rc = 0;
+	if ((rc = ensure(s.arena_work, off)) || (rc = ensure(s.pairA, n_total * 8 + 256)) || (rc = ensure(s.pairB, n_total * 8 + 256)))
+		return rc;
+	char *base = (char *)s.arena_work.p;
+	gr.arena_dyn = d_arena;
+	gr.arena_ent = (ArenaEntry *)(base + o_ent);
+	gr.arena_cap = (u32)std::min<u64>(cap, 0xFFFFFFF0ull);
+	aw.arena_off = (u32 *)(base + o_aoff);
+	aw.item_off = (u32 *)(base + o_ioff);
+	aw.bucket_hi = (u64 *)(base + o_hi);
+	aw.A = (u64 *)s.pairA.p;
+	aw.B = (u64 *)s.pairB.p;
+	aw.ghist = (u64 *)((char *)d_arena + up256((size_t)AR_DYN_WORDS * 4));
+	aw.dbase = (u64 *)(base + o_dbase);
+	aw.status = (u32 *)(base + o_status);
+	aw.status_stride = (u32)(stride / 4);
+	aw.S0 = gr.S[0];
+	return 0;
+}
+/* detect -> plan -> gather -> scan -> passes -> finish; nothing listed: launches that return */
+int arena_sort_group(const GroupTail &t, const std::vector<BinPlan> &bins, const GrpRank &gr, const ArenaWork &aw, u32 rbits, u32 ar_pass_max, u32 *d_flag)
+{
+	Slot &s = t.s;
+	u32 *err = err_ptr(s), *dyn = gr.arena_dyn;
+	/* tuning / debugging: persistent workgroups per kernel */
+	static const u32 g_gather = env_positive("KMC_HIP_ARENA_GRID_GATHER", 256u * 2u), g_sweep = env_positive("KMC_HIP_ARENA_GRID_SWEEP", 256u * 2u),
+	                 g_finish = env_positive("KMC_HIP_ARENA_GRID_FINISH", 256u * 2u);
+	GrpDetect gd = {};
+	gd.g = gr.g;
+	u64 blocks = 0;
+	for (size_t i = 0; i < bins.size(); ++i) {
+		gd.blk_prefix[i] = (u32)blocks;
+		gd.n[i] = bins[i].n_rec;
+		blocks += (bins[i].n_rec + 64 * BD_STRIDE - 1) / (64 * BD_STRIDE);
+	}
+	gd.blk_prefix[bins.size()] = (u32)blocks;
+	k_bucket_detect<<<dim3((u32)((blocks + 3) / 4)), dim3(256), 0, s.stream>>>(gr, gd, rbits);
+	k_arena_plan<<<dim3(1), dim3(AR_THREADS), 0, s.stream>>>(gr, aw, rbits, d_flag);
+	k_arena_gather<<<dim3(g_gather), dim3(AR_THREADS), (size_t)ar_pass_max * 1024, s.stream>>>(gr, aw, rbits, ar_pass_max);
+	k_hist_scan<<<dim3(ar_pass_max), dim3(256), 0, s.stream>>>(aw.ghist, aw.dbase);
+	ArenaDebug dbg; /* KMC_HIP_ARENA_DEBUG (host_arena_debug.hip.h); level 0 by default */
+	if (dbg.level >= 2)
+		if (int rc = arena_debug_gather(s, gr, aw, rbits, dbg))
+			return rc;
+	for (u32 pass = 0; pass < ar_pass_max; ++pass) {
+		if (dbg.level >= 2) {
+			if (int rc = arena_debug_pass(s, gr, aw, pass, dbg))
+				return rc;
+			if (dbg.level >= 3)
+				continue; /* the pass was enqueued there, by the ordinary kernel */
+		}
+		k_onesweep_dyn<1><<<dim3(g_sweep), dim3(RS_BLOCK), rs_lds_bytes<1>(), s.stream>>>((pass & 1u) ? aw.B : aw.A, (pass & 1u) ? aw.A : aw.B, dyn + AR_M, pass,
+		                                                                                  aw.dbase + (size_t)pass * 256, aw.dbase + (size_t)AR_MAX_PASS * 256,
+		                                                                                  aw.status + (size_t)pass * aw.status_stride, dyn + AR_PASS_TICKET + pass, err);
+	}
+	if (dbg.level)
+		if (int rc = arena_debug_finish(s, gr, aw, rbits, ar_pass_max, dbg))
+			return rc;
+	k_arena_finish<<<dim3(g_finish * (AR_THREADS / AF_THREADS)), dim3(AF_THREADS), 0, s.stream>>>(gr, aw, t.P, rbits, t.n_sh, t.lut_entries, t.lut_mask, err);
+	return 0;
+}
+
 /* ---- rank groups (default since round 4): the array is ordered by its top bytes only; k_bucket_rank puts every bucket-aligned tile of every bin in order
  * inside LDS and counts it there, straight into the tile's span of the free record array; then the fold and the gather of the two-phase output. A tile has
  * two output slots (one per chunk: a tile that outgrows the capacity is taken by two workgroups). ---- */
@@ -496,16 +589,11 @@ int rank_group(Slot &s, const std::vector<BinPlan> &bins, u64 *sorted, u64 *scra
 {
 	if (bins.empty())
 		return 0;
-	u32 *err = err_ptr(s);
-	const bool use_lut = lut_entries && !P.without_output && !P.kff;
-	const u32 n_sh = !use_lut ? 1u : lut_shards_for(lut_entries);
-	const u32 rec_bytes = P.sbytes + P.cbytes;
 	constexpr u64 S = BrCfg<SIZE>::STRIDE;
+	GroupTail tail(s, P, lut_entries);
 	GrpBounds gbn = {};
 	GrpRank gr = {};
-	GrpFold gf = {};
-	GrpGather gg = {};
-	gbn.g = gr.g = gg.g = (u32)bins.size();
+	gbn.g = gr.g = (u32)bins.size();
 	u64 wins = 0, items = 0;
 	for (const BinPlan &b : bins) {
 		items += (b.n_rec + S - 1) / S + 1;
@@ -522,36 +610,18 @@ int rank_group(Slot &s, const std::vector<BinPlan> &bins, u64 *sorted, u64 *scra
 		const u64 bin_wins = (b.n_rec + S - 1) / S;
 		gbn.item_prefix[i] = (u32)items;
 		gr.win_prefix[i] = (u32)wins;
-		gg.tile_prefix[i] = (u32)(2 * wins);
-		u64 *lut_base = b.d_lut;
-		if (use_lut && n_sh > 1)
-			lut_base = zero_ptr<u64>(s, b.off_lutsh);
-		else if (lut_entries && !P.kff && b.d_lut) /* also without output: the caller's LUT is zero-filled by the callee (include/kmc_hip.h) */
-			HIPCHK(hipMemsetAsync(b.d_lut, 0, lut_entries * 8, s.stream));
-		gbn.S[i] = sorted + b.rec_off * (d_recs_indirect ? 1 : SIZE);
-		gr.S[i] = sorted + b.rec_off * (d_recs_indirect ? 1 : SIZE);
-		gbn.n[i] = gf.n[i] = b.n_rec;
-		gbn.bounds[i] = bounds + items;
-		gr.bounds[i] = bounds + items;
+		gbn.S[i] = gr.S[i] = sorted + b.rec_off * (d_recs_indirect ? 1 : SIZE);
+		gbn.n[i] = b.n_rec;
+		gr.bounds[i] = gbn.bounds[i] = bounds + items;
 		gr.scratch[i] = (uint8_t *)(scratch + b.rec_off * SIZE);
 		gr.giant_T[i] = d_recs_indirect ? (u64 *)s.recC.p + b.rec_off * SIZE : nullptr; /* k_giant_tiles sorts records in place: it gathers a listed tile's records here first */
-		gr.status[i] = zero_ptr<u64>(s, b.off_cp_status);
 		gr.chunk_src[i] = chunk_src + 2 * wins;
-		gr.lut_base[i] = lut_base;
-		gr.tally[i] = zero_ptr<u64>(s, b.off_tally);
-		gf.tally[i] = gr.tally[i];
-		gf.stats[i] = b.d_stats;
-		gf.lut_base[i] = lut_base;
-		gf.lut_out[i] = b.d_lut;
-		gf.status[i] = gr.status[i];
-		gf.n_tiles[i] = (u32)(2 * bin_wins);
-		gf.out_bytes[i] = b.d_out_bytes;
-		gf.out_capacity[i] = b.out_capacity;
-		gg.scratch[i] = gr.scratch[i];
-		gg.prefix[i] = gr.status[i];
-		gg.out[i] = b.d_out;
-		gg.out_capacity[i] = b.out_capacity;
-		gg.src_rec[i] = gr.chunk_src[i];
+		BinTail bt;
+		if (int rc = tail.add_bin(i, b, 2 * wins, 2 * bin_wins, gr.scratch[i], gr.chunk_src[i], bt)) /* two output slots per tile */
+			return rc;
+		gr.status[i] = bt.status;
+		gr.lut_base[i] = bt.lut_base;
+		gr.tally[i] = bt.tally;
 		items += bin_wins + 1;
 		wins += bin_wins;
 	}
@@ -562,60 +632,12 @@ int rank_group(Slot &s, const std::vector<BinPlan> &bins, u64 *sorted, u64 *scra
 	const bool giant_list = wins < (1ull << GT_CUT_SHIFT);
 	gr.giant = giant_list ? d_giant : nullptr;
 	gr.rec_base = d_recs_indirect;
-	gg.tile_prefix[bins.size()] = (u32)(2 * wins);
-	/* The arena (one-word records): every bucket beyond BR_MID records is disjoint from every other, a giant one owns a tile — n_total / BR_MID + wins entries can never be
-	 * exceeded. Work area: entries | arena_off | item_off | bucket numbers | digit bases | look-back rows of up to AR_MAX_PASS passes over up to n_total records. */
+	const u32 rbits = sp.key_bits - sp.hbits();
 	ArenaWork aw = {};
 	u32 ar_pass_max = 0;
-	const u32 rbits = sp.key_bits - sp.hbits();
-	if constexpr (SIZE == 1) {
-		if (d_arena && wins < (1ull << 30) && n_total < (1ull << 40)) {
-			static const u64 cap_limit = [] { /* tests: a list too short for the group's buckets — the plan is dropped, the group comes back through LSD passes */
-				const char *e = getenv("KMC_HIP_ARENA_CAP");
-				return e ? (u64)strtoull(e, nullptr, 10) : ~0ull;
-			}();
-			const u64 cap = std::min<u64>(n_total / BR_MID + wins + 16, cap_limit);
-			const u64 max_tiles = (std::min<u64>(n_total, AR_MAX_RECORDS) + RsCfg<1>::TILE - 1) / RsCfg<1>::TILE;
-			u32 obits = 0;
-			while (obits < 32 && (1ull << obits) < cap)
-				++obits;
-			ar_pass_max = std::min<u32>(AR_MAX_PASS, (rbits + obits + 7) / 8);
-			size_t off = 0;
-			const size_t o_ent = off;
-			off += up256(cap * sizeof(ArenaEntry));
-			const size_t o_aoff = off;
-			off += up256((cap + 1) * 4);
-			const size_t o_ioff = off;
-			off += up256((cap + 1) * 4);
-			const size_t o_hi = off;
-			off += up256(cap * 8);
-			const size_t o_dbase = off;
-			off += up256((size_t)(AR_MAX_PASS + 1) * 256 * 8);
-			const size_t o_status = off;
-			const size_t stride = up256(max_tiles * 256 * 4);
-			off += stride * ar_pass_max;
-			if (int rc = ensure(s.arena_work, off))
-				return rc;
-			if (int rc = ensure(s.pairA, n_total * 8 + 256))
-				return rc;
-			if (int rc = ensure(s.pairB, n_total * 8 + 256))
-				return rc;
-			char *base = (char *)s.arena_work.p;
-			gr.arena_dyn = d_arena;
-			gr.arena_ent = (ArenaEntry *)(base + o_ent);
-			gr.arena_cap = (u32)std::min<u64>(cap, 0xFFFFFFF0ull);
-			aw.arena_off = (u32 *)(base + o_aoff);
-			aw.item_off = (u32 *)(base + o_ioff);
-			aw.bucket_hi = (u64 *)(base + o_hi);
-			aw.A = (u64 *)s.pairA.p;
-			aw.B = (u64 *)s.pairB.p;
-			aw.ghist = (u64 *)((char *)d_arena + up256((size_t)AR_DYN_WORDS * 4));
-			aw.dbase = (u64 *)(base + o_dbase);
-			aw.status = (u32 *)(base + o_status);
-			aw.status_stride = (u32)(stride / 4);
-			aw.S0 = gr.S[0];
-		}
-	}
+	if (SIZE == 1 && d_arena && wins < (1ull << 30) && n_total < (1ull << 40))
+		if (int rc = plan_arena(s, gr, aw, ar_pass_max, d_arena, rbits, wins, n_total))
+			return rc;
 	hipEvent_t e0 = nullptr, e1 = nullptr;
 	if (s.timed) {
 		if (int rc = ls_event_pair(s, e0, e1, n_total))
@@ -626,199 +648,20 @@ int rank_group(Slot &s, const std::vector<BinPlan> &bins, u64 *sorted, u64 *scra
 		k_bucket_bounds<1><<<dim3((u32)((items + 3) / 4)), dim3(256), 0, s.stream>>>(gbn, (u32)S, 64u, 32u);
 	else
 		k_bucket_bounds<SIZE><<<dim3((u32)((items + 3) / 4)), dim3(256), 0, s.stream>>>(gbn, (u32)S, sp.key_bits, sp.hbits());
-	const u32 lut_mask = P.lut_prefix_len ? (u32)((1ull << (2 * P.lut_prefix_len)) - 1) : 0u;
-	static const size_t lds_pad = [] { /* experiments: more dynamic LDS than the kernel uses = fewer workgroups per CU (room for another stream's kernels beside it) */
-		const char *e = getenv("KMC_HIP_RANK_LDS_PAD");
-		const size_t v = e ? (size_t)strtoull(e, nullptr, 10) : (size_t)0;
-		return v > 32 * 1024 ? (size_t)32 * 1024 : v;
-	}();
-	bool arena_ran = false;
-	if constexpr (SIZE == 1) {
-		if (gr.arena_dyn) { /* the buckets beyond BR_MID records, sorted together (arena_sort.hip.h); nothing listed: launches that return */
-			arena_ran = true;
-			u32 *dyn = gr.arena_dyn;
-			auto grid_of = [](const char *name) -> u32 { /* tuning / debugging: persistent workgroups per kernel */
-				const char *e = getenv(name);
-				const int v = e ? atoi(e) : 0;
-				return v > 0 ? (u32)v : 256u * 2u;
-			};
-			static const u32 g_gather = grid_of("KMC_HIP_ARENA_GRID_GATHER"), g_sweep = grid_of("KMC_HIP_ARENA_GRID_SWEEP"), g_finish = grid_of("KMC_HIP_ARENA_GRID_FINISH");
-			GrpDetect gd = {};
-			gd.g = gr.g;
-			u64 blocks = 0;
-			for (size_t i = 0; i < bins.size(); ++i) {
-				gd.blk_prefix[i] = (u32)blocks;
-				gd.n[i] = bins[i].n_rec;
-				blocks += (bins[i].n_rec + 64 * BD_STRIDE - 1) / (64 * BD_STRIDE);
-			}
-			gd.blk_prefix[bins.size()] = (u32)blocks;
-			k_bucket_detect<<<dim3((u32)((blocks + 3) / 4)), dim3(256), 0, s.stream>>>(gr, gd, rbits);
-			k_arena_plan<<<dim3(1), dim3(AR_THREADS), 0, s.stream>>>(gr, aw, rbits, d_flag);
-			k_arena_gather<<<dim3(g_gather), dim3(AR_THREADS), (size_t)ar_pass_max * 1024, s.stream>>>(gr, aw, rbits, ar_pass_max);
-			k_hist_scan<<<dim3(ar_pass_max), dim3(256), 0, s.stream>>>(aw.ghist, aw.dbase);
-			static const bool debug_steps = getenv("KMC_HIP_ARENA_DEBUG") && atoi(getenv("KMC_HIP_ARENA_DEBUG")) >= 2;
-			std::vector<u64> dbg_prev;
-			auto debug_step = [&](int pass) -> int { /* diagnostics: the arena after the gather (pass -1) / after pass `pass`, against what the host makes of the step's input */
-				HIPCHK(hipStreamSynchronize(s.stream));
-				u32 h_dyn[AR_DYN_WORDS];
-				HIPCHK(hipMemcpy(h_dyn, dyn, sizeof h_dyn, hipMemcpyDeviceToHost));
-				const u32 M = h_dyn[AR_M], ne = h_dyn[AR_N_ENT], np = h_dyn[AR_N_PASS];
-				if (!M || pass >= (int)np)
-					return 0;
-				std::vector<u64> cur(M);
-				HIPCHK(hipMemcpy(cur.data(), (pass & 1) ? aw.B : aw.A, (size_t)M * 8, hipMemcpyDeviceToHost)); /* pass -1 -> A (odd as a bit pattern: & 1 == 1)... handled below */
-				if (pass < 0) {
-					HIPCHK(hipMemcpy(cur.data(), aw.A, (size_t)M * 8, hipMemcpyDeviceToHost));
-					std::vector<u32> off(ne + 1);
-					std::vector<ArenaEntry> ent(ne);
-					HIPCHK(hipMemcpy(off.data(), aw.arena_off, (size_t)(ne + 1) * 4, hipMemcpyDeviceToHost));
-					HIPCHK(hipMemcpy(ent.data(), gr.arena_ent, (size_t)ne * sizeof(ArenaEntry), hipMemcpyDeviceToHost));
-					const u64 rmask = rbits >= 64 ? ~0ull : ((1ull << rbits) - 1);
-					u64 bad = 0, first = ~0ull, badoff = 0;
-					std::vector<u64> slice;
-					u64 run = 0;
-					for (u32 e = 0; e < ne; ++e) {
-						if (off[e] != run)
-							++badoff;
-						run += ent[e].len;
-						slice.resize(ent[e].len);
-						HIPCHK(hipMemcpy(slice.data(), aw.S0 + (ent[e].w0 & ((1ull << 40) - 1)), (size_t)ent[e].len * 8, hipMemcpyDeviceToHost));
-						for (u32 i = 0; i < ent[e].len; ++i)
-							if (off[e] + i < M && cur[off[e] + i] != (((u64)e << rbits) | (slice[i] & rmask))) {
-								if (!bad)
-									first = off[e] + i;
-								++bad;
-							}
-					}
-					std::vector<u64> gh((size_t)AR_MAX_PASS * 256), want((size_t)AR_MAX_PASS * 256, 0);
-					HIPCHK(hipMemcpy(gh.data(), aw.ghist, gh.size() * 8, hipMemcpyDeviceToHost));
-					for (u32 i = 0; i < M; ++i)
-						for (u32 b = 0; b < np; ++b)
-							++want[b * 256 + ((cur[i] >> (8 * b)) & 255)];
-					u64 badh = 0;
-					for (size_t i = 0; i < (size_t)np * 256; ++i)
-						badh += gh[i] != want[i];
-					fprintf(stderr, "[arena debug] gather: %llu of %u records differ from the host's (first %llu), %llu offsets off (sum %llu), %llu histogram cells differ\n", (unsigned long long)bad, M,
-					        (unsigned long long)first, (unsigned long long)badoff, (unsigned long long)run, (unsigned long long)badh);
-				} else {
-					HIPCHK(hipMemcpy(cur.data(), (pass & 1) ? aw.A : aw.B, (size_t)M * 8, hipMemcpyDeviceToHost)); /* pass p writes B when p is even */
-					std::vector<u64> want(dbg_prev);
-					std::stable_sort(want.begin(), want.end(), [&](u64 a, u64 b) { return ((a >> (8 * pass)) & 255) < ((b >> (8 * pass)) & 255); });
-					u64 bad = 0, first = ~0ull;
-					for (u32 i = 0; i < M; ++i)
-						if (cur[i] != want[i]) {
-							if (!bad)
-								first = i;
-							++bad;
-						}
-					fprintf(stderr, "[arena debug] pass %d: %llu of %u records differ from a stable sort of the pass's input by its digit (first %llu)\n", pass, (unsigned long long)bad, M,
-					        (unsigned long long)first);
-					u32 shown = 0;
-					for (u32 i = 0; i < M && shown < 12; ++i)
-						if (cur[i] != want[i]) {
-							u64 where = ~0ull; /* where the host expected the record the device put here */
-							for (u32 j = 0; j < M; ++j)
-								if (want[j] == cur[i]) {
-									where = j;
-									break;
-								}
-							fprintf(stderr, "[arena debug]   at %u: device %016llx host %016llx (the device's record belongs at %lld)\n", i, (unsigned long long)cur[i], (unsigned long long)want[i], (long long)where);
-							++shown;
-						}
-				}
-				dbg_prev.swap(cur);
-				return 0;
-			};
-			if (debug_steps)
-				if (int rc = debug_step(-1))
-					return rc;
-			for (u32 pass = 0; pass < ar_pass_max; ++pass) {
-				if (debug_steps && pass)
-					if (int rc = debug_step((int)pass - 1))
-						return rc;
-				static const bool debug_static = getenv("KMC_HIP_ARENA_DEBUG") && atoi(getenv("KMC_HIP_ARENA_DEBUG")) >= 3;
-				if (debug_static) { /* diagnostics: the pass by the ordinary kernel, its length read back by the host */
-					HIPCHK(hipStreamSynchronize(s.stream));
-					u32 h_dyn[AR_DYN_WORDS];
-					HIPCHK(hipMemcpy(h_dyn, dyn, sizeof h_dyn, hipMemcpyDeviceToHost));
-					if (h_dyn[AR_M] && pass < h_dyn[AR_N_PASS]) {
-						const u32 tiles = (h_dyn[AR_M] + RsCfg<1>::TILE - 1) / RsCfg<1>::TILE;
-						k_onesweep<1><<<dim3(tiles), dim3(RS_BLOCK), rs_lds_bytes<1>(), s.stream>>>((pass & 1u) ? aw.B : aw.A, (pass & 1u) ? aw.A : aw.B, h_dyn[AR_M], pass,
-						                                                                         aw.dbase + (size_t)pass * 256, aw.dbase + (size_t)AR_MAX_PASS * 256,
-						                                                                         aw.status + (size_t)pass * aw.status_stride, dyn + AR_PASS_TICKET + pass, tiles, err);
-					}
-					continue;
-				}
-				k_onesweep_dyn<1><<<dim3(g_sweep), dim3(RS_BLOCK), rs_lds_bytes<1>(), s.stream>>>((pass & 1u) ? aw.B : aw.A, (pass & 1u) ? aw.A : aw.B, dyn + AR_M, pass,
-				                                                                                  aw.dbase + (size_t)pass * 256, aw.dbase + (size_t)AR_MAX_PASS * 256,
-				                                                                                  aw.status + (size_t)pass * aw.status_stride, dyn + AR_PASS_TICKET + pass, err);
-			}
-			if (debug_steps)
-				if (int rc = debug_step((int)ar_pass_max - 1))
-					return rc;
-			static const bool debug = getenv("KMC_HIP_ARENA_DEBUG") != nullptr;
-			if (debug) { /* is the arena in order, and is every entry's slice the multiset of its bucket? (the stream is drained: diagnostics only) */
-				HIPCHK(hipStreamSynchronize(s.stream));
-				u32 h_dyn[AR_DYN_WORDS];
-				HIPCHK(hipMemcpy(h_dyn, dyn, sizeof h_dyn, hipMemcpyDeviceToHost));
-				const u32 M = h_dyn[AR_M], ne = h_dyn[AR_N_ENT], np = h_dyn[AR_N_PASS];
-				fprintf(stderr, "[arena debug] entries %u records %u passes %u (max %u) items %u heavy %u overflow %u rbits %u\n", ne, M, np, ar_pass_max, h_dyn[AR_N_ITEMS], 0u,
-				        h_dyn[AR_OVERFLOW], rbits);
-				if (M) {
-					std::vector<u64> ar(M);
-					std::vector<u32> off(ne + 1);
-					std::vector<ArenaEntry> ent(ne);
-					HIPCHK(hipMemcpy(ar.data(), (np & 1u) ? aw.B : aw.A, (size_t)M * 8, hipMemcpyDeviceToHost));
-					HIPCHK(hipMemcpy(off.data(), aw.arena_off, (size_t)(ne + 1) * 4, hipMemcpyDeviceToHost));
-					HIPCHK(hipMemcpy(ent.data(), gr.arena_ent, (size_t)ne * sizeof(ArenaEntry), hipMemcpyDeviceToHost));
-					u64 inversions = 0, first_inv = ~0ull;
-					for (u32 i = 1; i < M; ++i)
-						if (ar[i - 1] > ar[i]) {
-							if (!inversions)
-								first_inv = i;
-							++inversions;
-						}
-					u64 bad_entries = 0, first_bad = ~0ull, bad_ord = 0;
-					const u64 rmask = rbits >= 64 ? ~0ull : ((1ull << rbits) - 1);
-					std::vector<u64> slice;
-					for (u32 e = 0; e < ne; ++e) {
-						const u64 gpos = ent[e].w0 & ((1ull << 40) - 1);
-						slice.resize(ent[e].len);
-						HIPCHK(hipMemcpy(slice.data(), aw.S0 + gpos, (size_t)ent[e].len * 8, hipMemcpyDeviceToHost));
-						for (auto &x : slice)
-							x = ((u64)e << rbits) | (x & rmask);
-						std::sort(slice.begin(), slice.end());
-						bool ok = off[e + 1] - off[e] == ent[e].len;
-						for (u32 i = 0; ok && i < ent[e].len; ++i)
-							ok = ar[off[e] + i] == slice[i];
-						for (u32 i = off[e]; i < off[e + 1] && i < M; ++i)
-							if ((ar[i] >> rbits) != e)
-								++bad_ord;
-						if (!ok) {
-							if (!bad_entries)
-								first_bad = e;
-							++bad_entries;
-						}
-					}
-					fprintf(stderr, "[arena debug] inversions %llu (first at %llu), entries whose slice is not their bucket in order: %llu (first %llu), records under a foreign ordinal %llu\n",
-					        (unsigned long long)inversions, (unsigned long long)first_inv, (unsigned long long)bad_entries, (unsigned long long)first_bad, (unsigned long long)bad_ord);
-				}
-			}
-			k_arena_finish<<<dim3(g_finish * (AR_THREADS / AF_THREADS)), dim3(AF_THREADS), 0, s.stream>>>(gr, aw, P, rbits, n_sh, lut_entries, lut_mask, err);
-		}
-	}
-	/* every tile ranked and counted inside LDS (with the arena: its buckets beyond BR_MID records are in order by now and keep their places) */
-	k_bucket_rank<SIZE, true><<<dim3((u32)wins, 2), dim3(BrCfg<SIZE>::THREADS), br_lds_bytes<SIZE>() + lds_pad, s.stream>>>(gr, P, sp.key_bits, sp.hbits(), n_sh, lut_entries, lut_mask, d_flag);
-	/* the tiles with a bucket beyond the LDS capacity (k-mers repeated thousands of times), one workgroup each; nothing listed: a launch that returns */
-	if (!arena_ran && giant_list)
-		k_giant_tiles<SIZE><<<dim3((u32)std::min<u64>(wins, 256 * (1024 / GT_THREADS))), dim3(GT_THREADS), 0, s.stream>>>(gr, P, (u32)S, sp.key_bits, sp.hbits(), n_sh, lut_entries, lut_mask, err);
+	/* experiments: more dynamic LDS than the kernel uses = fewer workgroups per CU (room for another stream's kernels beside it) */
+	static const size_t lds_pad = (size_t)env_count("KMC_HIP_RANK_LDS_PAD", 0, 32 * 1024);
+	/* the arena: the buckets beyond BR_MID records, in order and in their places before the tiles are ranked */
+	if (gr.arena_dyn)
+		if (int rc = arena_sort_group(tail, bins, gr, aw, rbits, ar_pass_max, d_flag))
+			return rc;
+	/* every tile ranked and counted inside LDS */
+	k_bucket_rank<SIZE, true><<<dim3((u32)wins, 2), dim3(BrCfg<SIZE>::THREADS), br_lds_bytes<SIZE>() + lds_pad, s.stream>>>(gr, P, sp.key_bits, sp.hbits(), tail.n_sh, lut_entries, tail.lut_mask, d_flag);
+	/* without the arena: the tiles with a bucket beyond the LDS capacity (k-mers repeated thousands of times), one workgroup each; nothing listed: a launch that returns */
+	if (!gr.arena_dyn && giant_list)
+		k_giant_tiles<SIZE><<<dim3((u32)std::min<u64>(wins, 256 * (1024 / GT_THREADS))), dim3(GT_THREADS), 0, s.stream>>>(gr, P, (u32)S, sp.key_bits, sp.hbits(), tail.n_sh, lut_entries, tail.lut_mask, err_ptr(s));
 	if (s.timed)
 		HIPCHK(hipEventRecord(e1, s.stream));
-	k_compact_fold<<<dim3((u32)bins.size()), dim3(256), 0, s.stream>>>(gf, use_lut ? n_sh : 1u, lut_entries, 1u, rec_bytes, err);
-	if (!P.without_output)
-		k_compact_gather<<<dim3((u32)((2 * wins + 3) / 4)), dim3(256), 0, s.stream>>>(gg, rec_bytes, (u64)SIZE * 8);
-	HIPCHK(hipGetLastError());
-	return 0;
+	return tail.fold_and_gather(gr.g, 2 * wins, true, !P.without_output, (u64)SIZE * 8);
 }
 
 /* ---- a group of bins, everything device resident -------------------------------------------------------------------
@@ -829,11 +672,7 @@ int rank_group(Slot &s, const std::vector<BinPlan> &bins, u64 *sorted, u64 *scra
  * own is a group of one. */
 u32 group_capacity(u32 k, bool small_bins)
 {
-	static const int limit = [] {
-		const char *e = getenv("KMC_HIP_GROUP"); /* 1 = every bin on its own */
-		const int v = e ? atoi(e) : GRP_MAX;
-		return v < 1 ? 1 : (v > GRP_MAX ? GRP_MAX : v);
-	}();
+	static const int limit = std::max(1, std::min<int>(env_int("KMC_HIP_GROUP", GRP_MAX), GRP_MAX)); /* 1 = every bin on its own */
 	const u32 words = (k + 31) / 32;
 	const u32 spare = 8 * ((2 * k + 7) / 8) - 2 * k; /* bits of the top digit above the k-mer: tags that cost no pass */
 	const u32 room = 64 * words - 2 * k;             /* bits of the record above the k-mer */
@@ -852,8 +691,7 @@ constexpr u64 GROUP_MAX_RECORD_BYTES = 6ull << 30; /* per record array of a grou
                               * k = 55 21.3 -> 22.7 (16-byte gathers waste half of every HBM sector: finisher 1.81 -> 2.91 ms, passes 3.92 -> 2.20) */
 #endif
 
-/* d_stats / d_out_bytes == NULL in a descriptor (groups of one only): the slot's own small block. No caller passes NULL any more (the host
- * boundary writes to its HbRes block; the multi-device bin and the compaction hook fill their BinPlan themselves): the fallbacks below can go */
+/* every descriptor names its d_stats and d_out_bytes: the public entries refuse NULL, the host boundary writes to its HbRes block, the counting session to its own */
 template <int SIZE>
 int run_group_device_t(Slot &s, const DevParams &P, const kmc_hip_bin_desc *const *descs, u32 g, u64 lut_entries, bool classic, u32 *d_flag, bool *used_hybrid)
 {
@@ -864,6 +702,8 @@ int run_group_device_t(Slot &s, const DevParams &P, const kmc_hip_bin_desc *cons
 	u64 N = 0;
 	for (u32 i = 0; i < g; ++i) {
 		const kmc_hip_bin_desc &d = *descs[i];
+		if (!d.d_stats || !d.d_out_bytes)
+			return fail(KMC_HIP_EINTERNAL, "a bin descriptor without d_stats / d_out_bytes");
 		if ((d.n_rec == 0) != (d.size == 0))
 			return fail(KMC_HIP_ECORRUPT, "exactly one of size / n_rec is zero");
 		if (d.n_rec == 0)
@@ -896,10 +736,7 @@ int run_group_device_t(Slot &s, const DevParams &P, const kmc_hip_bin_desc *cons
 	/* default run (round 4): only the top bytes of the key go through HBM passes, every tile is put in order inside LDS by k_bucket_rank and counted there (fused:
 	 * whenever a tile's records fit its span of the free array; else, one-word records only, the tile is sorted in place and k_compact follows). Where the rank
 	 * plan does not apply (too many key bits left below the buckets, tiny groups, redo runs): LSD passes over every byte + k_compact */
-	static const bool fuse_enabled = [] {
-		const char *e = getenv("KMC_HIP_RANK_FUSE"); /* 0 (A/B runs): one-word records ranked in place + k_compact, wider ones LSD passes over every byte */
-		return !e || atoi(e) != 0;
-	}();
+	static const bool fuse_enabled = env_on("KMC_HIP_RANK_FUSE"); /* 0 (A/B runs): one-word records ranked in place + k_compact, wider ones LSD passes over every byte */
 	const bool can_fuse = count_applicable<SIZE>(P);
 	const bool by_rank = !classic && hybrid_mode() == 1 && rank_enabled() && (SIZE == 1 || (can_fuse && fuse_enabled));
 	const SortPlan sp = plan_sort<SIZE>(N, key_bytes, 2 * k + tag_bits, !by_rank, by_rank);
@@ -913,10 +750,7 @@ int run_group_device_t(Slot &s, const DevParams &P, const kmc_hip_bin_desc *cons
 	 * bytes (exactly the digits of those passes) above the record's number in the group —, sorted by k_onesweep<1>; the records stay where k_expand wrote them and
 	 * k_bucket_rank gathers each tile's records by number. Per record 4 x 16 bytes of passes + 8 written + 8 SIZE gathered instead of 4 x 16 SIZE (k = 127: ~130
 	 * instead of ~290 bytes per k-mer). k_giant_tiles (which sorts a tile's records in place) first gathers a listed tile's records into its slice of a third array. */
-	static const bool indirect_enabled = [] {
-		const char *e = getenv("KMC_HIP_INDIRECT"); /* 0 (A/B runs): records of every width go through the passes themselves */
-		return !e || atoi(e) != 0;
-	}();
+	static const bool indirect_enabled = env_on("KMC_HIP_INDIRECT"); /* 0 (A/B runs): records of every width go through the passes themselves */
 	bool indirect = SIZE >= INDIRECT_MIN_WORDS && indirect_enabled && rank_fused && sp.local() && n_pass == 4 && fuse && N < (1ull << 32);
 	int rc = 0;
 	if (N && ((rc = ensure(s.recA, N * SIZE * 8 + 256)) || (rc = ensure(s.recB, N * SIZE * 8 + 256))))
@@ -936,19 +770,12 @@ int run_group_device_t(Slot &s, const DevParams &P, const kmc_hip_bin_desc *cons
 	                                    rank_tiles, rank_fused && SIZE == 1 && arena_enabled());
 	if ((rc = apply_plan(s, z))) /* ONE memset per group: small block, bitmaps, look-back words, histograms, LUT and tally shards, scatter status */
 		return rc;
-	for (BinPlan &b : bins) { /* resolved only AFTER apply_plan: growing the zero region moves the small block */
-		if (!b.d_stats)
-			b.d_stats = small_ptr<u64>(s, SM_STATS);
-		if (!b.d_out_bytes)
-			b.d_out_bytes = small_ptr<u64>(s, SM_OUTBYTES);
-	}
 	for (u32 i = 0; i < g; ++i) { /* empty bins: zero results, nothing else */
 		const kmc_hip_bin_desc &d = *descs[i];
 		if (d.n_rec)
 			continue;
-		u64 *st = d.d_stats ? (u64 *)d.d_stats : small_ptr<u64>(s, SM_STATS), *ob = d.d_out_bytes ? (u64 *)d.d_out_bytes : small_ptr<u64>(s, SM_OUTBYTES);
-		HIPCHK(hipMemsetAsync(st, 0, 4 * 8, s.stream));
-		HIPCHK(hipMemsetAsync(ob, 0, 8, s.stream));
+		HIPCHK(hipMemsetAsync(d.d_stats, 0, 4 * 8, s.stream));
+		HIPCHK(hipMemsetAsync(d.d_out_bytes, 0, 8, s.stream));
 		if (lut_entries && !P.without_output)
 			HIPCHK(hipMemsetAsync(d.d_lut, 0, lut_entries * 8, s.stream));
 	}
@@ -1062,13 +889,10 @@ int drain_redo(Slot &s)
 				fprintf(stderr, " %llu", (unsigned long long)d.n_rec);
 			fprintf(stderr, "\n");
 		}
-		if (no_redo) {
-			note_redo();
-			any = true;
-			continue;
-		}
 		any = true;
 		note_redo();
+		if (no_redo)
+			continue;
 		/* the fused rank kernels name the BINS whose tiles they could not take (bits 16 + the bin's number among the group's non-empty bins: one k-mer beyond
 		 * GT_MAX_RECORDS copies — a satellite); the other bins of the group are complete and stay as they are: each flagged bin comes back alone, a group of one
 		 * through LSD passes over every byte (round 5; before, the whole group of up to 16 bins did). Any low bit: a producer that speaks for the group. */
@@ -1107,20 +931,8 @@ int drain_redo(Slot &s)
 }
 
 /* one bin = a group of one */
-int run_bin_device(Slot &s, const DevParams &P, const uint8_t *d_in, u64 size, u64 n_rec, const u64 *d_pack_start, u64 n_packs, uint8_t *d_out,
-                   u64 out_capacity, u64 *d_out_bytes, u64 *d_lut, u64 lut_entries, u64 *d_stats, bool classic = false, bool async = false)
+int run_bin_device(Slot &s, const DevParams &P, const kmc_hip_bin_desc &d, u64 lut_entries, bool classic = false, bool async = false)
 {
-	kmc_hip_bin_desc d;
-	d.d_superkmers = d_in;
-	d.size = size;
-	d.n_rec = n_rec;
-	d.d_pack_start = (const uint64_t *)d_pack_start;
-	d.n_packs = n_packs;
-	d.d_out = d_out;
-	d.out_capacity = out_capacity;
-	d.d_out_bytes = (uint64_t *)d_out_bytes;
-	d.d_lut = (uint64_t *)d_lut;
-	d.d_stats = (uint64_t *)d_stats;
 	const kmc_hip_bin_desc *p = &d;
 	if (async)
 		return run_group_async(s, P, &p, 1, lut_entries);

@@ -100,13 +100,36 @@ int ensure(DBuf &b, size_t bytes)
 	return 0;
 }
 
+/* tuning and test switches, read from the environment variable `name` (a caller that must not read its switch twice keeps the value in a function-local static):
+ * the positive integer in it, else `dflt` */
+u32 env_positive(const char *name, u32 dflt)
+{
+	const char *e = getenv(name);
+	return e && atoi(e) > 0 ? (u32)atoi(e) : dflt;
+}
+/* on, unless the variable holds 0 (or no number at all) */
+bool env_on(const char *name)
+{
+	const char *e = getenv(name);
+	return !e || atoi(e) != 0;
+}
+/* the integer in it, of either sign, else `dflt` */
+int env_int(const char *name, int dflt)
+{
+	const char *e = getenv(name);
+	return e ? atoi(e) : dflt;
+}
+/* the count (of bytes, of entries) in it, at most `cap`, else `dflt` */
+u64 env_count(const char *name, u64 dflt, u64 cap = ~0ull)
+{
+	const char *e = getenv(name);
+	return e ? std::min<u64>(strtoull(e, nullptr, 10), cap) : dflt;
+}
+
 /* is `p` host memory the device can reach by DMA as it is (hipHostMalloc / hipHostRegister)? Ordinary memory is staged through a pinned buffer of the slot. */
 bool host_ptr_is_pinned(const void *p)
 {
-	static const bool always = [] {
-		const char *e = getenv("KMC_HIP_STAGE_PAGEABLE"); /* 0: copy straight from / to pageable memory (rounds 1-3) */
-		return e && atoi(e) == 0;
-	}();
+	static const bool always = !env_on("KMC_HIP_STAGE_PAGEABLE"); /* 0: copy straight from / to pageable memory (rounds 1-3) */
 	if (always || !p)
 		return true;
 	hipPointerAttribute_t at;
@@ -305,13 +328,6 @@ template <int MAX, int W = 1, class F> int by_words(u32 words, F &&f)
 		return by_words<MAX, W + 1>(words, f);
 	else
 		return fail(KMC_HIP_EINVAL, "records of " + std::to_string(words) + " words: this entry takes 1.." + std::to_string(MAX));
-}
-
-/* a tuning or test switch: the positive integer in the environment variable `name`, else `dflt` */
-u32 env_positive(const char *name, u32 dflt)
-{
-	const char *e = getenv(name);
-	return e && atoi(e) > 0 ? (u32)atoi(e) : dflt;
 }
 
 int set_dev(kmc_hip_ctx *ctx, int dev)
@@ -588,7 +604,8 @@ struct DevTemps {
 
 /* The rest of this translation unit, in the order it is compiled (round 5: one 3 400-line file split along its entry families; no kernel and no statement changed).
  * tests/emu.py build_hostlib inlines these files again before it rewrites the kernel launches for the CPU emulation. */
-#include "host_plan_and_groups.hip.h" /* the sort planner, the HBM passes, the groups of bins (front end, LSD / bucket-count / rank finishers), the redo of flagged groups */
+#include "host_arena_debug.hip.h" /* KMC_HIP_ARENA_DEBUG: the arena's steps read back and checked by the host (diagnostics, off by default) */
+#include "host_plan_and_groups.hip.h" /* the sort planner, the HBM passes, the groups of bins (front end, shared tail, LSD / rank finishers, the arena's plan and launches), the redo of flagged groups */
 #include "host_hooks_and_order.hip.h" /* stage-isolating test hooks (device side) and the globally ordered database */
 #include "host_multi_device_bin.hip.h" /* one bin over all devices of the context */
 #include "host_cabi_stage2.hip.h" /* the C-ABI of stage 2: lifetime, narrow boundary, full boundary (one bin / several bins per call, device-resident batches) */
