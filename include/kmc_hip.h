@@ -547,6 +547,35 @@ int kmc_hip_smallk_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split
 int kmc_hip_smallk_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint64_t *dst);
 int kmc_hip_smallk_close(kmc_hip_ctx *ctx, int dev);
 
+/* ---- stage 0, signature statistics (added within ABI version 4, like kmc_hip_smallk_*) ----
+ * The reference decides which signature goes to which bin from a sample of the input: every CWStatsSplitter worker (splitter.h:118, splitter.cpp:878-925) runs
+ * CSplitter::CalcStats (splitter.cpp:439-533) over the parts of the stage-0 queue, which adds 1 + len - kmer_len per super-k-mer to stats[signature] (4^m + 1
+ * uint32 counters, entry 4^m the special signature); the workers' arrays are summed and CSignatureMapper::Init (s_mapper.h:141-235) builds the map from them. A
+ * super-k-mer is a maximal run of k-mers with one signature, so stats[s] is the number of k-mer windows whose signature is s. These entries keep ONE such array
+ * on `dev` (k_s1_sig_stats); the caller hands it to the reference's Init as one worker's array. Ask kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_SIGSTATS) first.
+ * _open : replaces the allocation and fill of CWStatsSplitter's constructor (splitter.cpp:878-893): allocates and zeroes 4^signature_len + 1 uint32 counters;
+ *         signature_len 5..11, signature_len <= kmer_len <= 256. Opening again with the same (kmer_len, signature_len) is a no-op, with another pair KMC_HIP_EINVAL.
+ * _part : replaces CSplitter::CalcStats for one part (with GetSeq splitter.cpp:88-421 and HomopolymerCompressSeq :424-435 in front): every window of kmer_len
+ *         valid symbols of every buffer GetSeq returns (compressed first with KMC_HIP_SPLIT_HOMOPOLYMER) adds one to the counter of its signature, the minimum
+ *         of norm[m-mer] over the window's m-mers (kmc_api/mmer.h:39-95). Uses kmer_len, signature_len, file_type (0, 1, 2, 4), line_cap, part_kind and flags
+ *         (only KMC_HIP_SPLIT_HOMOPOLYMER; any other bit is KMC_HIP_EINVAL) of `p`; n_bins, max_x and both_strands decide nothing, and no signature map is read.
+ *         *n_reads = titles in the part (as kmc_hip_split_part), *n_kmers = the windows added: the sum of the part's adds. Counters wrap at 2^32 like the
+ *         reference's. Returns 0, a negative code, or KMC_HIP_UNCOVERED for the malformed inputs kmc_hip_split_part answers it for. A call that does not return 0
+ *         leaves the array as it was: the kernel is launched only once the call can no longer fail. Calls on different slots of one device may run at once.
+ * _read : replaces CWStatsSplitter::GetStats (splitter.cpp:919-925): waits for everything the device's slots have launched, then copies entries
+ *         [first, first + count) to dst. The array is not cleared.
+ * _close: frees the array (kmc_hip_destroy does it too); none open is not an error. It waits for the kmc_hip_sigstats_part calls that are inside the library on
+ *         `dev`; a call that starts after it finds no array (KMC_HIP_EINVAL). */
+#define KMC_HIP_SPLIT_COVERS_SIGSTATS 0x107u /* kmc_hip_sigstats_open / _part / _read / _close (0x106 stays unknown, as 0x104 and 0x101 do) */
+int kmc_hip_sigstats_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t signature_len);
+int kmc_hip_sigstats_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint64_t *n_reads, uint64_t *n_kmers);
+int kmc_hip_sigstats_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint32_t *dst);
+int kmc_hip_sigstats_close(kmc_hip_ctx *ctx, int dev);
+/* Which entries of the array can be a signature at all: dst[s] = 1 for the m-mers CMmer::is_allowed accepts (kmc_api/mmer.h:39-64, the kernels' own s1_allowed),
+ * 0 for the others and for entry 4^signature_len; 4^signature_len + 1 bytes. CSignatureMapper::Init gives a bin to every allowed m-mer, also to those that never
+ * occur as a signature because their reverse complement is the smaller one — which a table of norm values cannot tell from a forbidden one. Needs no context. */
+int kmc_hip_sigstats_allowed(uint32_t signature_len, uint8_t *dst);
+
 /* ---- a counting session: reads in, one ordered database body out, no bin record leaves the device (added within ABI version 4, like kmc_hip_smallk_*) ----
  * The reference carries every part's bin records from stage 1 to stage 2 through the host: CKmerBinStorer appends each collector's buffer to its bin's file
  * (kb_storer.cpp), CKmerBinReader reads every file back as one bin image (kb_reader.h:141-190), the completer hands the sorted bins on (kb_completer.cpp:160-320). A

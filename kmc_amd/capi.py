@@ -84,6 +84,7 @@ SPLIT_COVERS_ESTIMATE = 0x102  # KMC_HIP_SPLIT_COVERS_ESTIMATE
 SPLIT_COVERS_SMALLK = 0x103  # KMC_HIP_SPLIT_COVERS_SMALLK: kmc_hip_smallk_open / _part / _read / _close (k <= 13 counted on the device)
 SMALLK_MAX_K = 13
 SPLIT_COVERS_COUNT = 0x105  # KMC_HIP_SPLIT_COVERS_COUNT: kmc_hip_count_open / _part / _finish / _order / _info / _timings / _close (a counting session; 0x104 stays unknown)
+SPLIT_COVERS_SIGSTATS = 0x107  # KMC_HIP_SPLIT_COVERS_SIGSTATS: kmc_hip_sigstats_open / _part / _read / _close (stage 0: signature statistics; 0x106 stays unknown)
 UNCOVERED = 1  # KMC_HIP_UNCOVERED: malformed text the kernels do not reproduce; nothing was produced
 SPLIT_LINE_CAP = (65536 + 1) * 8  # the reference's mem_part_pmm_reads (kmc.h:419, splitter.cpp:18): kmc_hip_split_params.line_cap of a front end
 SPLIT_COVERS_HOMOPOLYMER = 0x100  # KMC_HIP_SPLIT_COVERS_HOMOPOLYMER: ask kmc_hip_split_covers before setting the flag (an older library ignores it)
@@ -141,6 +142,7 @@ SYMBOLS = [
     "kmc_hip_split_reads_plan", "kmc_hip_split_reads_emit", "kmc_hip_split_reads_free",
     "kmc_hip_split_set_map", "kmc_hip_split_part", "kmc_hip_split_covers", "kmc_hip_estimate_open", "kmc_hip_estimate_read", "kmc_hip_estimate_close",
     "kmc_hip_smallk_open", "kmc_hip_smallk_part", "kmc_hip_smallk_read", "kmc_hip_smallk_close",
+    "kmc_hip_sigstats_open", "kmc_hip_sigstats_part", "kmc_hip_sigstats_read", "kmc_hip_sigstats_close", "kmc_hip_sigstats_allowed",
     "kmc_hip_db_set_op_device", "kmc_hip_db_query_reads_device",
     "kmc_hip_db_reduce_device", "kmc_hip_db_histogram_device", "kmc_hip_db_dump_device",
     "kmc_hip_db_expr_device",
@@ -234,6 +236,7 @@ def load():
         L.kmc_hip_smallk_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(SplitParams), vp, C.c_uint64, u64p, u64p]
         L.kmc_hip_smallk_read.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp]
         L.kmc_hip_smallk_close.argtypes = [vp, C.c_int]
+    bind_sigstats(L)
     if hasattr(L, "kmc_hip_db_set_op_device"):  # added within ABI version 4
         L.kmc_hip_db_set_op_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.POINTER(DbView), C.POINTER(DbOp), vp, C.c_uint64, vp, u64p, u64p]
     if hasattr(L, "kmc_hip_db_query_reads_device"):  # added within ABI version 4
@@ -264,6 +267,18 @@ def bind_count(L):
     L.kmc_hip_count_close.argtypes = [vp, vp]
     L.kmc_hip_count_close.restype = None
     L.kmc_hip_debug_gather_segments.argtypes = [vp, C.c_int, vp, vp, vp, C.c_uint64]
+
+
+def bind_sigstats(L):
+    """the prototypes of the stage-0 statistics on a loaded library (added within ABI version 4: ask kmc_hip_split_covers(SPLIT_COVERS_SIGSTATS))"""
+    if not hasattr(L, "kmc_hip_sigstats_open"):
+        return
+    vp = C.c_void_p
+    L.kmc_hip_sigstats_open.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32]
+    L.kmc_hip_sigstats_part.argtypes = [vp, C.c_int, C.c_int, C.POINTER(SplitParams), vp, C.c_uint64, u64p, u64p]
+    L.kmc_hip_sigstats_read.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp]
+    L.kmc_hip_sigstats_close.argtypes = [vp, C.c_int]
+    L.kmc_hip_sigstats_allowed.argtypes = [C.c_uint32, vp]
 
 
 def _vp(a: np.ndarray):
@@ -649,6 +664,62 @@ class CountSession:
         if self.h:
             self.ctx.L.kmc_hip_count_close(self.ctx.h, self.h)
             self.h = None
+
+
+def allowed_signatures(signature_len: int, L=None) -> np.ndarray:
+    """bool[4^m + 1]: the m-mers that can be a signature (CMmer::is_allowed, as the kernels compute it); the last entry, the special signature's, is False.
+    L: a loaded library (a Context's L); by default the in-tree one"""
+    L = L or load()
+    bind_sigstats(L)
+    out = np.zeros((1 << (2 * signature_len)) + 1, dtype=np.uint8)
+    rc = L.kmc_hip_sigstats_allowed(signature_len, _vp(out))
+    if rc:
+        raise KmcHipError(rc, L.kmc_hip_last_error(None).decode())
+    return out.astype(bool)
+
+
+class SigStats:
+    """kmc_hip_sigstats: the stage-0 statistics of one (k, signature length) on a device — stats[s] = the k-mer windows whose signature is s, 4^m + 1 uint32
+    (include/kmc_hip.h). ctx: a Context, or anything with its L, h and _chk."""
+
+    def __init__(self, ctx, k: int, signature_len: int, dev: int = 0):
+        self.ctx, self.dev, self.k, self.m, self.open = ctx, dev, k, signature_len, False
+        if not hasattr(ctx.L, "kmc_hip_sigstats_open") or ctx.L.kmc_hip_split_covers(SPLIT_COVERS_SIGSTATS) != 1:
+            raise KmcHipError(-1, f"{lib_path()} has no kmc_hip_sigstats_open")
+        bind_sigstats(ctx.L)
+        ctx._chk(ctx.L.kmc_hip_sigstats_open(ctx.h, dev, k, signature_len))
+        self.open = True
+
+    @property
+    def entries(self) -> int:
+        return (1 << (2 * self.m)) + 1
+
+    def part_rc(self, text, file_type: int = 1, line_cap: int = SPLIT_LINE_CAP, part_kind: int = 0, flags: int = 0, slot: int = 0):
+        """one part; -> (return code, reads, windows added): the code is 0, UNCOVERED or negative, nothing is raised"""
+        p = SplitParams(self.k, self.m, 0, 0, 0, file_type, line_cap, part_kind, flags)
+        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        n_reads, n_kmers = C.c_uint64(0), C.c_uint64(0)
+        rc = self.ctx.L.kmc_hip_sigstats_part(self.ctx.h, self.dev, slot, C.byref(p), _vp(t) if t.size else None, t.size, C.byref(n_reads), C.byref(n_kmers))
+        return rc, n_reads.value, n_kmers.value
+
+    def part(self, text, **kw):
+        """one part; -> (reads, windows added). KMC_HIP_UNCOVERED raises like an error: the statistics are as they were"""
+        rc, n_reads, n_kmers = self.part_rc(text, **kw)
+        if rc == UNCOVERED:
+            raise KmcHipError(rc, "KMC_HIP_UNCOVERED: the part's text is malformed in a way the device splitter does not reproduce")
+        self.ctx._chk(rc)
+        return n_reads, n_kmers
+
+    def read(self, first: int = 0, count: int = None) -> np.ndarray:
+        count = self.entries - first if count is None else count
+        out = np.zeros(max(count, 1), dtype=np.uint32)
+        self.ctx._chk(self.ctx.L.kmc_hip_sigstats_read(self.ctx.h, self.dev, first, count, _vp(out)))
+        return out[:count]
+
+    def close(self):
+        if self.open:
+            self.ctx.L.kmc_hip_sigstats_close(self.ctx.h, self.dev)
+            self.open = False
 
 
 # ---- synthetic stage-2 inputs (libkmc_synth.so)

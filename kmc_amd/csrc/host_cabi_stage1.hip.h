@@ -280,7 +280,7 @@ int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, 
 int kmc_hip_split_covers(uint32_t what)
 {
 	return what <= 2 || what == 4 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER || what == KMC_HIP_SPLIT_COVERS_ESTIMATE || what == KMC_HIP_SPLIT_COVERS_SMALLK ||
-	               what == KMC_HIP_SPLIT_COVERS_COUNT
+	               what == KMC_HIP_SPLIT_COVERS_COUNT || what == KMC_HIP_SPLIT_COVERS_SIGSTATS
 	           ? 1
 	           : 0;
 }
@@ -311,7 +311,7 @@ int kmc_hip_estimate_close(kmc_hip_ctx *ctx, int dev)
 	return accum_close(d.est, d);
 }
 
-/* ---- what kmc_hip_split_part and kmc_hip_smallk_part share: the refusals that are not an entry's own, the call past them, the chain's return code ---- */
+/* ---- what kmc_hip_split_part, kmc_hip_smallk_part and kmc_hip_sigstats_part share: the refusals that are not an entry's own, the call past them, the chain's return code ---- */
 namespace {
 int s1_part_check(const char *who, const kmc_hip_split_params *p, u64 size)
 {
@@ -550,6 +550,105 @@ int kmc_hip_smallk_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split
 		if (F.n >= p->kmer_len) {
 			u64 *d_total = (u64 *)be.alloc(8);
 			s1_smallk_part(be, (const int8_t *)F.d_codes, F.n, p->kmer_len, part.sp.both_strands, d_table, d_total, max_wgs, lds_k);
+			be.d2h(&counted, d_total, 8);
+		}
+		*n_kmers = counted;
+	} catch (const S1BackendFailure &f) {
+		return fail_hip(f.what, f.e);
+	}
+	*n_reads = R.n_reads;
+	return 0;
+}
+
+/* ---- stage 0 on the device: the one array of signature statistics the reference's CSignatureMapper::Init reads (CWStatsSplitter splitter.h:118, splitter.cpp:878-925;
+ * CSplitter::CalcStats splitter.cpp:439-533) ---- */
+int kmc_hip_sigstats_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t signature_len)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	if (signature_len < 5 || signature_len > 11 || kmer_len < signature_len || kmer_len > (uint32_t)S1_MAX_K)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_sigstats_open: signature_len 5..11, signature_len <= kmer_len <= 256");
+	return accum_open(ctx->devs[dev]->sigstats, "kmc_hip_sigstats_open", "an array of signature statistics", kmer_len, signature_len, 0, ((u64)1 << (2 * signature_len)) + 1, sizeof(u32));
+}
+
+int kmc_hip_sigstats_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint32_t *dst)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	Dev &d = *ctx->devs[dev];
+	return accum_read(d.sigstats, d, "kmc_hip_sigstats_read", "array of signature statistics", first, count, dst, sizeof(u32));
+}
+
+int kmc_hip_sigstats_close(kmc_hip_ctx *ctx, int dev)
+{
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	Dev &d = *ctx->devs[dev];
+	return accum_close(d.sigstats, d);
+}
+
+int kmc_hip_sigstats_allowed(uint32_t signature_len, uint8_t *dst)
+{
+	if (!dst || signature_len < 5 || signature_len > 11)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_sigstats_allowed: dst NULL or signature_len outside 5..11");
+	const u32 entries = 1u << (2 * signature_len);
+	for (u32 x = 0; x < entries; ++x)
+		dst[x] = s1_allowed(x, signature_len) ? 1 : 0;
+	dst[entries] = 0;
+	return 0;
+}
+
+int kmc_hip_sigstats_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint64_t *n_reads, uint64_t *n_kmers)
+{
+	const char *who = "kmc_hip_sigstats_part";
+	if (int rc = set_dev(ctx, dev))
+		return rc;
+	if (!p || (size && !text) || !n_reads || !n_kmers || slot < 0 || slot >= N_SLOTS)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_sigstats_part: bad argument");
+	if (p->signature_len < 5 || p->signature_len > 11 || p->kmer_len < p->signature_len || p->kmer_len > (uint32_t)S1_MAX_K)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_sigstats_part: unsupported parameters (signature_len 5..11, signature_len <= kmer_len <= 256)");
+	if (p->flags & ~KMC_HIP_SPLIT_HOMOPOLYMER)
+		return fail(KMC_HIP_EINVAL, "kmc_hip_sigstats_part: unknown bit in flags (KMC_HIP_SPLIT_ESTIMATE included: the reference's stage 0 estimates nothing)");
+	if (int rc = s1_part_check(who, p, size))
+		return rc;
+	Dev &d = *ctx->devs[dev];
+	u32 *d_table = nullptr;
+	AccumHold table_hold;
+	{
+		std::lock_guard<std::mutex> lck(d.sigstats.mtx);
+		if (!d.sigstats.p)
+			return fail(KMC_HIP_EINVAL, "kmc_hip_sigstats_part without kmc_hip_sigstats_open on this device");
+		if (d.sigstats.par[0] != p->kmer_len || d.sigstats.par[1] != p->signature_len)
+			return fail(KMC_HIP_EINVAL, "kmc_hip_sigstats_part: the open array has another kmer_len / signature_len");
+		d_table = (u32 *)d.sigstats.p;
+		table_hold.take(d.sigstats);
+	}
+	*n_reads = *n_kmers = 0;
+	Slot &s = d.slot[slot];
+	std::lock_guard<std::mutex> lck(s.mtx);
+	/* the front half's share of kmc_hip_split_part's work area, as kmc_hip_smallk_part takes it */
+	const bool hc = (p->flags & KMC_HIP_SPLIT_HOMOPOLYMER) != 0;
+	const size_t per_byte = p->file_type == 4 ? 8 + (hc ? 4 : 0) : (p->file_type == 2 ? 8 : 6) + (hc ? 2 : 0);
+	S1Part part;
+	if (int rc = part.begin(d, slot, p, text, size, per_byte))
+		return rc;
+	S1HipBackend &be = part.be;
+	/* measurement and test switches, like KMC_HIP_S1_SMALLK_LDS_K: the result does not depend on them */
+	const u32 max_wgs = env_positive("KMC_HIP_S1_SIGSTATS_WGS", S1_STATS_WGS);
+	u32 lds_m = S1_STATS_LDS_M_DEFAULT;
+	if (const char *e = getenv("KMC_HIP_S1_SIGSTATS_LDS_M"))
+		lds_m = (u32)atoi(e) <= S1_STATS_LDS_M ? (u32)atoi(e) : lds_m;
+	S1PartResult R;
+	S1Front F;
+	try {
+		uint8_t *d_text = part.upload();
+		if (int rc = part.code(who, s1_front_part(be, d_text, part.size, part.ends_with_newline(), part.sp, R, F, true), R))
+			return rc;
+		/* nothing below fails because of the part: only now may its windows reach the array */
+		u64 counted = 0;
+		if (F.n >= p->kmer_len) {
+			u64 *d_total = (u64 *)be.alloc(8);
+			s1_sigstats_part(be, (const int8_t *)F.d_codes, F.n, p->kmer_len, p->signature_len, d_table, d_total, max_wgs, lds_m);
 			be.d2h(&counted, d_total, 8);
 		}
 		*n_kmers = counted;

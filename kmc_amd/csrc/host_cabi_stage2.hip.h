@@ -179,7 +179,7 @@ void kmc_hip_destroy(kmc_hip_ctx *ctx)
 			(void)hipFree(d->xchg.p);
 		if (d->d_sig_map)
 			(void)hipFree(d->d_sig_map);
-		for (Accum *a : {&d->est, &d->smallk})
+		for (Accum *a : {&d->est, &d->smallk, &d->sigstats})
 			if (a->p)
 				(void)hipFree(a->p);
 		for (auto &a : d->s1_arena)

@@ -259,7 +259,7 @@ struct Slot {
 	bool without_output = false;
 };
 
-/* A device array that stage-1 part calls add into, one per device and kind (the estimator's counters, the small-k table): opened with parameters — the same ones
+/* A device array that stage-1 part calls add into, one per device and kind (the estimator's counters, the small-k table, the signature statistics): opened with parameters — the same ones
  * open it again as a no-op, others are refused —, read by range once the slots' streams are idle, closed only when no part call holds it (accum_* below). */
 struct Accum {
 	void *p = nullptr; /* nullptr = none open */
@@ -300,6 +300,7 @@ struct Dev {
 	DBuf s1_arena[N_SLOTS]; /* stage 1: grow-only work area of kmc_hip_split_part, one per stream slot */
 	Accum est;    /* stage 1: the two u32 counter arrays of kmc_hip_estimate_open (type 0, then type 1: 2^r entries each); par: kmer_len, s, r */
 	Accum smallk; /* stage 1, small k: the 4^k u64 counters of kmc_hip_smallk_open; par: kmer_len, both_strands */
+	Accum sigstats; /* stage 0: the 4^m + 1 u32 counters of kmc_hip_sigstats_open; par: kmer_len, signature_len */
 };
 
 u32 counter_bytes(u64 cutoff_max, u64 counter_max) { return kmc_counter_bytes(cutoff_max, counter_max); }

@@ -357,4 +357,20 @@ template <class B> void s1_smallk_part(B &be, const int8_t *d_codes, u64 n, u32 
 		S1_LAUNCH(B, be, (k_s1_smallk_count<0>), dim3((u32)grid), dim3(S1_BLOCK), d_codes, n, k, both_strands, d_table, d_total);
 }
 
+/* Stage 0 (CSplitter::CalcStats, splitter.cpp:439-533): every window of k valid codes of the stream the front half leaves (S1Front::d_codes, n) adds one to the entry
+ * of its signature among the 4^m + 1 32-bit counters at d_table (k_s1_sig_stats); *d_total (zeroed by the caller) receives the number of windows. Like
+ * s1_smallk_part the caller launches this once the part can no longer fail: a part that is refused or not covered leaves the table untouched. max_wgs: the
+ * persistent workgroups at most; lds_m: the largest m whose table is kept in LDS (at most S1_STATS_LDS_M; 0 = every m adds straight into d_table). */
+template <class B> void s1_sigstats_part(B &be, const int8_t *d_codes, u64 n, u32 k, u32 m, u32 *d_table, u64 *d_total, u32 max_wgs = S1_STATS_WGS, u32 lds_m = S1_STATS_LDS_M_DEFAULT)
+{
+	if (n < k)
+		return;
+	const u64 tiles = (n - k + 1 + S1_STATS_TILE - 1) / S1_STATS_TILE;
+	const u64 grid = tiles < max_wgs ? tiles : (max_wgs ? max_wgs : 1);
+	if (m <= lds_m && m <= S1_STATS_LDS_M)
+		S1_LAUNCH(B, be, (k_s1_sig_stats<(int)S1_STATS_LDS_M>), dim3((u32)grid), dim3(S1_BLOCK), d_codes, n, k, m, d_table, d_total);
+	else
+		S1_LAUNCH(B, be, (k_s1_sig_stats<0>), dim3((u32)grid), dim3(S1_BLOCK), d_codes, n, k, m, d_table, d_total);
+}
+
 #endif

@@ -1509,24 +1509,32 @@ constexpr u32 S1_SMALLK_MAX_K = 13, S1_SMALLK_LDS_K = 7, S1_SMALLK_WGS = 1024;
 constexpr u64 S1_SMALLK_MAX_TILES_PER_WG = 1ull << 19;
 static_assert(S1_SMALLK_MAX_K - 1 <= 16 && S1_TXT_PER == 16, "the halo is one 16-byte load; a strip is a thread's 16 positions");
 
-/* called by whole waves only */
-__device__ __forceinline__ void s1_smallk_add(u64 *__restrict__ table, u32 idx, u32 cnt, bool emit)
+/* called by whole waves only. T: the table's counters (u64: the small-k table; u32: k_s1_sig_stats's, which wrap like the reference's). REPEAT: another round for
+ * as long as the last one merged lanes — a satellite puts the lanes of a wave on two signatures, and the second one's lanes would add one by one; random text, where
+ * the first adding lane is alone with its index, still pays one round */
+template <class T, bool REPEAT = false> __device__ __forceinline__ void s1_smallk_add(T *__restrict__ table, u32 idx, u32 cnt, bool emit)
 {
-	const u64 todo = __ballot(emit);
-	if (!todo) /* wave-uniform */
-		return;
-	const u32 lane = threadIdx.x & 63u, leader = (u32)__ffsll((unsigned long long)todo) - 1u;
-	const u32 at = __shfl(idx, (int)leader);
-	const bool mine = emit && idx == at;
-	const u64 same = __ballot(mine);
-	if (__popcll((unsigned long long)same) > 1) { /* wave-uniform */
-		const u32 sum = __shfl(wave_sum<u32>(mine ? cnt : 0u), 0);
-		if (lane == leader)
-			__hip_atomic_fetch_add(table + at, (u64)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		emit = emit && !mine;
+	const u32 lane = threadIdx.x & 63u;
+	for (;;) {
+		const u64 todo = __ballot(emit);
+		if (!todo) /* wave-uniform */
+			return;
+		const u32 leader = (u32)__ffsll((unsigned long long)todo) - 1u;
+		const u32 at = __shfl(idx, (int)leader);
+		const bool mine = emit && idx == at;
+		const u64 same = __ballot(mine);
+		if (__popcll((unsigned long long)same) > 1) { /* wave-uniform */
+			const u32 sum = __shfl(wave_sum<u32>(mine ? cnt : 0u), 0);
+			if (lane == leader)
+				__hip_atomic_fetch_add(table + at, (T)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			emit = emit && !mine;
+			if (REPEAT)
+				continue;
+		}
+		break;
 	}
 	if (emit)
-		__hip_atomic_fetch_add(table + idx, (u64)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__hip_atomic_fetch_add(table + idx, (T)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 template <int LDS_K>
@@ -1600,6 +1608,96 @@ __global__ void __launch_bounds__(S1_BLOCK) k_s1_smallk_count(const int8_t *__re
 			const u32 v = s_tab[i];
 			if (v)
 				__hip_atomic_fetch_add(table + i, (u64)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+	}
+	const u64 wsum = wave_sum<u64>((u64)counted);
+	if ((tid & 63u) == 0)
+		s_sum[tid >> 6] = wsum;
+	__syncthreads();
+	if (tid == 0) {
+		u64 all = 0;
+#pragma unroll
+		for (u32 w = 0; w < (u32)S1_BLOCK / 64; ++w)
+			all += s_sum[w];
+		if (all)
+			__hip_atomic_fetch_add(total, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+}
+
+/* ------------------------------------------------------------------------------------------------ stage 0: signature statistics
+ * CSplitter::CalcStats (splitter.cpp:439-533) walks the stage-0 sample as ProcessReads walks a part and adds 1 + len - kmer_len per super-k-mer to
+ * _stats[signature] (uint32, wrapping). A super-k-mer is a maximal run of k-mers with one signature (the top of this file), so stats[s] is the number of valid
+ * k-mer windows whose signature is s: a histogram over the code stream the front half leaves (the raw stream, or the -hc stream with -hc). The pieces of
+ * over-long lines, long-read parts and multi-line sequences overlap by k - 1 symbols: every window lies in exactly one piece, S1_PIECE_MARK is ignored.
+ *
+ * k_s1_sig_stats<LDS_M>: 4^m + 1 32-bit counters in HBM, entry 4^m the special signature (no allowed m-mer in the window). Workgroups are persistent over tiles
+ * of S1_STATS_TILE start positions (blockIdx.x, blockIdx.x + gridDim.x, ...); the tile's signatures come into LDS from s1_signatures_to_lds, S1_SUB calls of
+ * S1_STATS_TILE / S1_SUB positions, each with its k - 1 halo codes — the m-mer, norm and window-minimum code of k_s1_signatures and k_s1_cut<true>. A thread then
+ * walks a strip of S1_STATS_PER consecutive positions (an odd number: the lanes' LDS reads are bank-conflict free) and merges equal neighbours: neighbouring
+ * k-mers share a signature for (k - m + 1) / 2 positions on average, and a run is one add of its length. Which positions of a strip a run came from does not
+ * matter to the sum, so a pending run survives invalid positions and is added when another signature follows, or at the strip's end.
+ *   LDS_M = 0: relaxed agent-scope adds without return straight into the table, behind the wave aggregation of s1_smallk_add, repeated while it merges lanes:
+ *     inside a homopolymer or a satellite the lanes of a wave all hold one or two signatures, and each becomes one add; random text pays one round.
+ *   LDS_M > 0 (m <= LDS_M): a workgroup-private table of 4^LDS_M + 1 counters in LDS, flushed once per workgroup, non-zero entries only. 32-bit and wrapping
+ *     like the table itself: the result does not depend on the switch.
+ * *total += the windows added, one add per workgroup. No look-back, no ticket, no spin loop. */
+constexpr int S1_STATS_PER = 4 * S1_SUB - 1, S1_STATS_TILE = S1_BLOCK * S1_STATS_PER, S1_STATS_SUBTILE = S1_STATS_TILE / S1_SUB;
+constexpr u32 S1_STATS_LDS_M = 7, S1_STATS_LDS_M_DEFAULT = 7, S1_STATS_WGS = 2048; /* _DEFAULT: the largest m that takes the LDS table unless the caller says otherwise */
+static_assert(S1_STATS_SUBTILE * S1_SUB == S1_STATS_TILE && S1_STATS_SUBTILE <= S1_TILE + 2, "a sub-tile is one call of s1_signatures_to_lds");
+
+template <int LDS_M>
+__global__ void __launch_bounds__(S1_BLOCK) k_s1_sig_stats(const int8_t *__restrict__ codes, u64 n, u32 k, u32 m, u32 *__restrict__ table, u64 *total)
+{
+	static_assert(LDS_M == 0 || (LDS_M >= 5 && LDS_M <= (int)S1_STATS_LDS_M), "4^LDS_M + 1 32-bit counters beside the tile's signatures");
+	constexpr u32 TAB = LDS_M ? (1u << (2 * LDS_M)) + 1u : 1u;
+	__shared__ S1SigLds L;
+	__shared__ u32 s_sig[S1_STATS_TILE];
+	__shared__ u32 s_tab[TAB];
+	__shared__ u64 s_sum[S1_BLOCK / 64];
+	const u32 tid = threadIdx.x;
+	const u32 entries = (1u << (2 * m)) + 1u; /* m <= LDS_M where there is an LDS table: the launcher's promise */
+	const u64 n_pos = n - k + 1;              /* n >= k: the launcher's promise. A position behind n - k starts no window: its signature is S1_NOSIG */
+	const u64 num_tiles = (n_pos + S1_STATS_TILE - 1) / S1_STATS_TILE;
+	if (LDS_M)
+		for (u32 i = tid; i < entries && i < TAB; i += S1_BLOCK)
+			s_tab[i] = 0;
+	u32 counted = 0;
+	for (u64 tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) { /* the same trips for every thread of the workgroup */
+		const u64 t0 = tile * S1_STATS_TILE;
+		/* every call begins and ends with a barrier: the strips of the tile before are walked when s_sig is written (first trip: the table is zero) */
+#pragma unroll 1
+		for (int sub = 0; sub < S1_SUB; ++sub)
+			s1_signatures_to_lds(codes, n, (long long)(t0 + (u64)sub * S1_STATS_SUBTILE), S1_STATS_SUBTILE, k, m, L, s_sig + sub * S1_STATS_SUBTILE);
+		const u32 l0 = tid * S1_STATS_PER;
+		u32 psig = 0, pcnt = 0; /* pcnt windows of signature psig wait to be added */
+#pragma unroll
+		for (int j = 0; j < S1_STATS_PER; ++j) {
+			const u32 sg = s_sig[l0 + j];
+			const bool hit = sg != S1_NOSIG;
+			const bool emit = hit && pcnt && sg != psig;
+			if (LDS_M) {
+				if (emit)
+					atomicAdd(&s_tab[psig], pcnt);
+			} else
+				s1_smallk_add<u32, true>(table, psig, pcnt, emit); /* every lane of the wave is here: the strips are equally long */
+			if (hit) {
+				pcnt = pcnt && sg == psig ? pcnt + 1u : 1u;
+				psig = sg;
+				++counted;
+			}
+		}
+		if (LDS_M) {
+			if (pcnt)
+				atomicAdd(&s_tab[psig], pcnt);
+		} else
+			s1_smallk_add<u32, true>(table, psig, pcnt, pcnt != 0);
+	}
+	if (LDS_M) {
+		__syncthreads();
+		for (u32 i = tid; i < entries && i < TAB; i += S1_BLOCK) {
+			const u32 v = s_tab[i];
+			if (v)
+				__hip_atomic_fetch_add(table + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		}
 	}
 	const u64 wsum = wave_sum<u64>((u64)counted);

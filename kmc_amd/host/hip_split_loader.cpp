@@ -36,6 +36,13 @@ struct SplitApi {
 	int (*sk_close)(kmc_hip_ctx *, int) = nullptr;
 	std::mutex sk_mtx;
 	std::vector<char> sk_on; /* per device: a small-k table was opened and not drained yet */
+	/* optional, added with KMC_HIP_SPLIT_COVERS_SIGSTATS: a library without them (or whose kmc_hip_split_covers does not know the capability) leaves stage 0 to the reference */
+	int (*ss_open)(kmc_hip_ctx *, int, uint32_t, uint32_t) = nullptr;
+	int (*ss_part)(kmc_hip_ctx *, int, int, const kmc_hip_split_params *, const uint8_t *, uint64_t, uint64_t *, uint64_t *) = nullptr;
+	int (*ss_read)(kmc_hip_ctx *, int, uint64_t, uint64_t, uint32_t *) = nullptr;
+	int (*ss_close)(kmc_hip_ctx *, int) = nullptr;
+	std::mutex ss_mtx;
+	std::vector<char> ss_on; /* per device: an array of signature statistics was opened and not drained yet */
 	kmc_hip_ctx *ctx = nullptr;
 	int n_dev = 1, n_slots = 1;
 	std::string err;
@@ -60,6 +67,10 @@ void bind()
 	g_split.sk_part = reinterpret_cast<decltype(g_split.sk_part)>(dlsym(so, "kmc_hip_smallk_part"));
 	g_split.sk_read = reinterpret_cast<decltype(g_split.sk_read)>(dlsym(so, "kmc_hip_smallk_read"));
 	g_split.sk_close = reinterpret_cast<decltype(g_split.sk_close)>(dlsym(so, "kmc_hip_smallk_close"));
+	g_split.ss_open = reinterpret_cast<decltype(g_split.ss_open)>(dlsym(so, "kmc_hip_sigstats_open"));
+	g_split.ss_part = reinterpret_cast<decltype(g_split.ss_part)>(dlsym(so, "kmc_hip_sigstats_part"));
+	g_split.ss_read = reinterpret_cast<decltype(g_split.ss_read)>(dlsym(so, "kmc_hip_sigstats_read"));
+	g_split.ss_close = reinterpret_cast<decltype(g_split.ss_close)>(dlsym(so, "kmc_hip_sigstats_close"));
 	if (!g_split.set_map || !g_split.split_part || !g_split.last_error) {
 		g_split.err = "libkmc_hip.so lacks kmc_hip_split_set_map / kmc_hip_split_part";
 		g_split.ctx = nullptr;
@@ -67,6 +78,7 @@ void bind()
 	g_split.map_hash.assign((size_t)g_split.n_dev, 0);
 	g_split.est_on.assign((size_t)g_split.n_dev, 0);
 	g_split.sk_on.assign((size_t)g_split.n_dev, 0);
+	g_split.ss_on.assign((size_t)g_split.n_dev, 0);
 }
 
 struct HipSplitEngine : KmcSplitEngine {
@@ -75,7 +87,7 @@ struct HipSplitEngine : KmcSplitEngine {
 	std::string err;
 	std::vector<uint8_t> recs;
 	std::vector<uint64_t> arrays; /* bin_off | bin_bytes | bin_kmers | bin_superkmers | bin_plus_x */
-	std::vector<uint32_t> drain_buf; /* estimate_drain: one chunk of one device's counters */
+	std::vector<uint32_t> drain_buf; /* estimate_drain, sigstats_drain: one chunk of one device's counters */
 	std::vector<uint64_t> sk_drain_buf; /* smallk_drain: one chunk of one device's table */
 
 	uint64_t map_hash = 0; /* of this run's map: a second KMC run in the same process (library API) with another map must not split with the first one's */
@@ -208,6 +220,76 @@ struct HipSplitEngine : KmcSplitEngine {
 		}
 		if (first + count == entries)
 			std::vector<uint64_t>().swap(sk_drain_buf);
+		return 0;
+	}
+	bool covers_signature_stats() const override
+	{
+		return g_split.ctx && g_split.covers && g_split.ss_open && g_split.ss_part && g_split.ss_read && g_split.ss_close && g_split.covers(KMC_HIP_SPLIT_COVERS_SIGSTATS) == 1;
+	}
+	int sigstats_open() override
+	{
+		if (!covers_signature_stats()) {
+			err = "HIP split engine: the library does not compute the signature statistics on the device";
+			return KMC_HIP_EINVAL;
+		}
+		std::lock_guard<std::mutex> lck(g_split.ss_mtx);
+		if (int rc = g_split.ss_open(g_split.ctx, dev, P.kmer_len, P.signature_len)) { /* a second engine on the device: the same pair, a no-op */
+			err = g_split.last_error(g_split.ctx);
+			return rc;
+		}
+		g_split.ss_on[dev] = 1;
+		return 0;
+	}
+	int sigstats_part(const uint8_t *text, uint64_t size, bool long_read, uint64_t &n_reads, uint64_t &n_kmers) override
+	{
+		if (!covers_signature_stats()) {
+			err = "HIP split engine: the library does not compute the signature statistics on the device";
+			return KMC_HIP_EINVAL;
+		}
+		kmc_hip_split_params hp;
+		hp.kmer_len = P.kmer_len;
+		hp.signature_len = P.signature_len;
+		hp.n_bins = hp.max_x = 0; /* not read */
+		hp.both_strands = P.both_strands ? 1u : 0u;
+		hp.file_type = (uint32_t)P.file_type;
+		hp.line_cap = P.line_cap;
+		hp.part_kind = long_read ? 1u : 0u;
+		hp.flags = P.homopolymer_compressed ? KMC_HIP_SPLIT_HOMOPOLYMER : 0u;
+		const int rc = g_split.ss_part(g_split.ctx, dev, slot, &hp, text, size, &n_reads, &n_kmers);
+		if (rc == KMC_HIP_UNCOVERED)
+			return KMC_SPLIT_UNCOVERED;
+		if (rc)
+			err = g_split.last_error(g_split.ctx);
+		return rc;
+	}
+	int sigstats_drain(uint64_t first, uint64_t count, uint32_t *dst) override
+	{
+		const uint64_t entries = ((uint64_t)1 << (2 * P.signature_len)) + 1;
+		if (!g_split.ctx || P.signature_len > 11 || count > ((uint64_t)1 << 23) || first > entries || count > entries - first) {
+			err = "HIP split engine: sigstats_drain outside the array, or more than 2^23 entries at once";
+			return KMC_HIP_EINVAL;
+		}
+		std::lock_guard<std::mutex> lck(g_split.ss_mtx);
+		drain_buf.resize(count);
+		for (int d = 0; d < g_split.n_dev; ++d) {
+			if (!g_split.ss_on[d])
+				continue;
+			if (int rc = g_split.ss_read(g_split.ctx, d, first, count, drain_buf.data())) {
+				err = g_split.last_error(g_split.ctx);
+				return rc;
+			}
+			for (uint64_t i = 0; i < count; ++i)
+				dst[i] += drain_buf[i];
+			if (first + count == entries) {
+				g_split.ss_on[d] = 0;
+				if (int rc = g_split.ss_close(g_split.ctx, d)) {
+					err = g_split.last_error(g_split.ctx);
+					return rc;
+				}
+			}
+		}
+		if (first + count == entries)
+			std::vector<uint32_t>().swap(drain_buf);
 		return 0;
 	}
 	int split_part(const uint8_t *text, uint64_t size, bool long_read, KmcSplitResult &out) override

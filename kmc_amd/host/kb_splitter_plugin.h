@@ -5,8 +5,8 @@
  * Drop-in for the reference's CWSplitter (splitter.h:100-113, splitter.cpp:814-867): the same class name, constructor, operator()(),
  * GetTotal() and destructor, so CKMC<SIZE>::ProcessStage1_impl (kmc.h:1274-1362) builds against it unchanged. Compiled in with
  * `-include kb_splitter_plugin.h` ahead of kmc_runner.cpp; the reference's own splitter.cpp is compiled with -DCWSplitter=CWSplitter_ref
- * (oracle/Makefile), which is what this header declares first: CSplitter stays the reference's for what is NOT this worker (stage 0's signature
- * statistics and the estimate-only worker use it directly, kmc.h:1100-1200; the small-k worker is CWSmallKSplitter_dev at the end of this header); this worker itself never calls it
+ * (oracle/Makefile), which is what this header declares first: CSplitter stays the reference's for what is NOT this worker (the estimate-only
+ * worker uses it directly, kmc.h:1100-1200; the small-k worker is CWSmallKSplitter_dev and stage 0's signature statistics CWStatsSplitter_dev at the end of this header); this worker itself never calls it
  * (see FAILS CLOSED below).
  *
  * Protocol kept from CWSplitter::operator() + CSplitter::ProcessReads + CKmerBinCollector:
@@ -30,8 +30,8 @@
  *             read of mem_part_pmm_reads bases or more.
  * Parts the reader labelled ReadType::long_read (queues.h:40) and lines of mem_part_pmm_reads symbols or more go through the engine like any other, and so
  * do the ReadType::na parts of multi-line FASTA (fastq_reader.cpp:399-468, :579-583) with an engine that covers them (file_type 2). With -hc the engine
- * compresses every return of GetSeq on its own, as ProcessReads does (splitter.cpp:575-581); stage 0 and the estimate worker stay the
- * reference's and honour the flag themselves (the small-k worker below passes it to its engine), and n_reads does not depend on it.
+ * compresses every return of GetSeq on its own, as ProcessReads does (splitter.cpp:575-581); the estimate worker stays the
+ * reference's and honours the flag itself (the small-k and stage-0 workers below pass it to their engines), and n_reads does not depend on it.
  * With --opt-out-size (ESTIMATE_AND_COUNT_KMERS) the reference's splitter hashes every k-mer a second time into Queues.ntHashEstimator (splitter.cpp:576-577),
  * an object that exists before the workers are constructed (kmc.h:1277-1293). Here the engine keeps those counters where it splits: every worker opens the
  * estimator of its engine's device with the object's own s and r, the LAST worker to finish adds the counters of every device into the object's arrays
@@ -583,5 +583,145 @@ public:
 };
 /* from here on (kmc.h is read after this header) the small-k worker of CKMC<SIZE> is the one above */
 #define CWSmallKSplitter CWSmallKSplitter_dev
+
+/* ---- the stage-0 worker (the signature statistics the signature -> bin map is built from: CKMC<SIZE>::buildSignatureMapping, kmc.h:974-1075) ----
+ * Drop-in for the reference's CWStatsSplitter (splitter.h:118-131, splitter.cpp:878-925): constructor (Params, Queues), operator()(), GetStats(uint32 *), so that
+ * kmc.h:1007-1054 builds against it unchanged and the reference's own CSignatureMapper::Init (s_mapper.h:141-235) runs on the result. The reference's class keeps
+ * its name and stays linkable (splitter.cpp defines it); this one has a name of its own, and the #define below points kmc.h at it.
+ * With an engine that covers_signature_stats() the parts of the stats queue are looked at where the engine does it, into ONE array per device (CSplitter::CalcStats
+ * adds 1 + len - kmer_len per super-k-mer: the number of k-mer windows per signature): the worker reserves and zeroes its own array from pmm_stats as the
+ * reference's does (kmc.h:438 sizes the pool for one per worker), pops parts, calls sigstats_part, steps the progress observer and frees each part; the LAST
+ * worker to finish adds every device's array into its own and the others hand over zeros. A part the engine answers KMC_SPLIT_UNCOVERED or an error for stops
+ * the run like a part of the bin worker does. With any other engine (the oracle and emulated engines, a library without kmc_hip_sigstats_*) — or one that lacks
+ * the job's format or -hc — stage 0 goes to the reference's CWStatsSplitter, as it did before this worker existed. The small-k mode builds no map and never
+ * constructs this worker. */
+typedef CWStatsSplitter CWStatsSplitter_ref;
+
+class CWStatsSplitter_dev {
+	CStatsPartQueue *spq;
+	CMemoryPool *pmm_fastq, *pmm_stats;
+	CKMCParams *params;
+	uint32 *stats = nullptr;
+	uint32 signature_len;
+	KMC::IProgressObserver *progressObserver;
+	std::unique_ptr<CWStatsSplitter_ref> ref; /* non-null: the reference's worker runs stage 0 */
+	std::unique_ptr<KmcSplitEngine> engine;
+	uint64 st_parts = 0, st_kmers = 0;
+	long long st_engine_ns = 0;
+
+	static std::atomic<int> &finished_workers()
+	{
+		static std::atomic<int> finished{0};
+		return finished;
+	}
+	void drain()
+	{
+		const uint64_t entries = ((uint64_t)1 << (2 * signature_len)) + 1, chunk = (uint64_t)1 << 23; /* 32 MB of counters at a time */
+		KmcTimeline::mark("stage 0: drain of the device statistics starts");
+		for (uint64_t at = 0; at < entries; at += chunk)
+			if (int rc = engine->sigstats_drain(at, entries - at < chunk ? entries - at : chunk, stats + at)) {
+				std::ostringstream ostr;
+				ostr << "Error: stage-1 split engine failed to hand over the signature statistics (code " << rc << "): " << engine->last_error();
+				CCriticalErrorHandler::Inst().HandleCriticalError(ostr.str());
+			}
+		KmcTimeline::mark("stage 0: device statistics merged");
+	}
+
+public:
+	CWStatsSplitter_dev(CKMCParams &Params, CKMCQueues &Queues)
+	{
+		spq = Queues.stats_part_queue.get();
+		pmm_fastq = Queues.pmm_fastq.get();
+		pmm_stats = Queues.pmm_stats.get();
+		params = &Params;
+		progressObserver = Params.progressObserver;
+		signature_len = Params.signature_len;
+		KmcSplitParams sp;
+		sp.kmer_len = Params.kmer_len;
+		sp.signature_len = Params.signature_len;
+		sp.n_bins = Params.n_bins;
+		sp.max_x = 0;
+		sp.both_strands = Params.both_strands ? 1 : 0;
+		sp.file_type = Params.file_type == InputType::FASTQ ? 1 : Params.file_type == InputType::MULTILINE_FASTA ? 2 : Params.file_type == InputType::BAM ? 4 : 0;
+		sp.line_cap = (uint64_t)Params.mem_part_pmm_reads;
+		sp.sig_to_bin = nullptr; /* the map is what this stage is for */
+		sp.homopolymer_compressed = Params.homopolymer_compressed ? 1 : 0;
+		static std::atomic<int> next_idx{0};
+		engine.reset(kmc_make_split_engine(sp, next_idx++ % (int)Params.n_splitters, (int)Params.n_splitters));
+		const bool covered = engine && engine->covers_signature_stats() && (Params.file_type != InputType::MULTILINE_FASTA || engine->covers_multiline_fasta()) &&
+		                     (Params.file_type != InputType::BAM || engine->covers_bam()) && (!Params.homopolymer_compressed || engine->covers_homopolymer_compression());
+		if (!covered) {
+			engine.reset();
+			ref = std::make_unique<CWStatsSplitter_ref>(Params, Queues); /* reserves its own array */
+			return;
+		}
+		pmm_stats->reserve(stats); /* splitter.cpp:887-888 */
+		std::fill_n(stats, ((size_t)1 << (2 * signature_len)) + 1, 0u);
+		finished_workers() = 0; /* every worker is constructed before any can finish (kmc.h:1009-1013), as in CWSplitter above */
+		if (int rc = engine->sigstats_open()) {
+			std::ostringstream ostr;
+			ostr << "Error: stage-1 split engine could not open the signature statistics (code " << rc << "): " << engine->last_error();
+			CCriticalErrorHandler::Inst().HandleCriticalError(ostr.str());
+		}
+	}
+	~CWStatsSplitter_dev()
+	{
+		if (stats)
+			pmm_stats->free(stats);
+	}
+
+	void operator()()
+	{
+		if (ref) {
+			(*ref)();
+			return;
+		}
+		KmcTimeline::mark_first_last("stage 0: first worker started", nullptr);
+		while (!spq->completed()) {
+			uchar *part;
+			uint64 size;
+			ReadType read_type;
+			if (!spq->pop(part, size, read_type))
+				continue;
+			if (read_type == ReadType::na && params->file_type != InputType::MULTILINE_FASTA && params->file_type != InputType::BAM)
+				CCriticalErrorHandler::Inst().HandleCriticalError("Error: stage 0 on the device got a part of ReadType::na");
+			uint64_t part_reads = 0, part_kmers = 0;
+			const auto t0 = std::chrono::steady_clock::now();
+			const int rc = engine->sigstats_part(part, size, read_type == ReadType::long_read, part_reads, part_kmers);
+			st_engine_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+			if (rc == KMC_SPLIT_UNCOVERED)
+				kmc_hip_s1_stop_uncovered_part(params->file_type, read_type);
+			if (rc != 0) {
+				std::ostringstream ostr;
+				ostr << "Error: stage-1 split engine failed in stage 0 (code " << rc << "): " << engine->last_error();
+				CCriticalErrorHandler::Inst().HandleCriticalError(ostr.str());
+			}
+			++st_parts;
+			st_kmers += part_kmers;
+			progressObserver->Step();
+			pmm_fastq->free(part);
+		}
+		if (++finished_workers() == (int)params->n_splitters)
+			drain();
+		engine.reset();
+		KmcTimeline::mark_first_last(nullptr, "stage 0: last worker done");
+		if (getenv("KMC_HIP_VERBOSE"))
+			fprintf(stderr, "[kmc_hip stage 0] worker: signature statistics on the device: %llu parts, %llu k-mers (%.3f s inside the engine)%s\n", (unsigned long long)st_parts,
+			        (unsigned long long)st_kmers, st_engine_ns * 1e-9, params->homopolymer_compressed ? ", homopolymer-compressed (-hc) on the device" : "");
+	}
+
+	void GetStats(uint32 *_stats)
+	{
+		if (ref) {
+			ref->GetStats(_stats);
+			return;
+		}
+		const uint32 size = (1u << (signature_len * 2)) + 1;
+		for (uint32 i = 0; i < size; ++i)
+			_stats[i] += stats[i];
+	}
+};
+/* from here on the stage-0 worker of CKMC<SIZE> is the one above */
+#define CWStatsSplitter CWStatsSplitter_dev
 
 #endif

@@ -76,6 +76,18 @@ struct KmcSplitEngine {
 	virtual int smallk_open() { return -1; }
 	virtual int smallk_part(const uint8_t * /*text*/, uint64_t /*size*/, bool /*long_read*/, uint64_t & /*n_reads*/, uint64_t & /*n_kmers*/) { return -1; }
 	virtual int smallk_drain(uint64_t /*first*/, uint64_t /*count*/, uint64_t * /*dst*/) { return -1; }
+	/* stage 0, the signature statistics (CWStatsSplitter, splitter.h:118, splitter.cpp:878-925, over CSplitter::CalcStats :439-533): the engine keeps ONE array of
+	 * 4^signature_len + 1 32-bit counters wherever its parts are looked at, instead of one per worker. An engine made for this path gets sig_to_bin = nullptr (the
+	 * map is what the statistics are for) and must not need n_bins or max_x; kmer_len, signature_len, file_type, line_cap and homopolymer_compressed count.
+	 * sigstats_open : makes the (zeroed) array of this engine's device; once per engine, in front of its first part. 0 or an error code.
+	 * sigstats_part : one part: n_reads as split_part gives it, n_kmers = the windows added (the sum of 1 + len - kmer_len over the part's super-k-mers). 0, a
+	 *                 negative error code or KMC_SPLIT_UNCOVERED; a call that does not return 0 has added nothing.
+	 * sigstats_drain: when every engine of the run has seen its last part: ADDS entries [first, first + count) of the array of every device one was opened on to
+	 *                 dst[0 .. count) (wrapping at 2^32), count <= 2^23; the call that takes the last entry also closes the arrays. 0 or an error code. */
+	virtual bool covers_signature_stats() const { return false; }
+	virtual int sigstats_open() { return -1; }
+	virtual int sigstats_part(const uint8_t * /*text*/, uint64_t /*size*/, bool /*long_read*/, uint64_t & /*n_reads*/, uint64_t & /*n_kmers*/) { return -1; }
+	virtual int sigstats_drain(uint64_t /*first*/, uint64_t /*count*/, uint32_t * /*dst*/) { return -1; }
 };
 
 /* Provided by exactly one engine implementation linked into the binary. */

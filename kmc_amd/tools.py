@@ -958,6 +958,92 @@ def count_signature_map(signature_len: int, n_bins: int, multiplier: int = COUNT
     return ((((sig * np.uint64(multiplier)) & np.uint64(0xFFFFFFFF)) >> np.uint64(8)) % np.uint64(n_bins)).astype(np.int32)
 
 
+COUNT_MAP_MIN_BINS = 64  # the reference's own minimum of -n (kmc_CLI/kmc.cpp); below it CSignatureMapper::Init's arithmetic breaks (n_bins 2: it assigns bin 2)
+
+
+def balanced_signature_map(stats: np.ndarray, signature_len: int, n_bins: int, allowed: np.ndarray = None) -> np.ndarray:
+    """CSignatureMapper::Init (s_mapper.h:141-235) restated: the signature -> bin map, int32[4^m + 1], from the stage-0 statistics (uint32[4^m + 1]: k-mer windows
+    per signature). Only allowed signatures take part, each with stats + 1000, in descending order (ties: ascending signature; the reference's std::sort leaves
+    ties unspecified, so its exact map is not reproduced). While more signatures are left than bins: one above the running mean (what is left / the bins that are
+    left) gets a bin alone, otherwise a bin takes, in that order, every signature that still fits under 1.1 x the mean. The rest get a bin each, the special
+    signature (entry 4^m) the bin behind the last one used; entries that are not allowed stay -1. allowed: bool[4^m + 1], by default the library's own
+    (capi.allowed_signatures). n_bins >= COUNT_MAP_MIN_BINS."""
+    size = (1 << (2 * signature_len)) + 1
+    stats = np.asarray(stats)
+    if stats.size != size:
+        raise ValueError(f"balanced_signature_map: {stats.size} statistics for signature length {signature_len}")
+    if n_bins < COUNT_MAP_MIN_BINS:
+        raise ValueError(f"balanced_signature_map: {n_bins} bins; the reference's mapper needs {COUNT_MAP_MIN_BINS} at least")
+    if allowed is None:
+        allowed = capi.allowed_signatures(signature_len)
+    out = np.full(size, -1, dtype=np.int32)
+    sig = np.flatnonzero(np.asarray(allowed, dtype=bool)[:size - 1])
+    w = stats[sig].astype(np.float64) + 1000.0
+    order = np.argsort(-w, kind="stable")  # descending weight, ascending signature among equals
+    sig, w = sig[order], w[order]
+    total = float(w.sum())
+    mean = total / n_bins
+    max_bin = 1.1 * mean
+    n, max_bins, bin_no = n_bins - 1, n_bins - 1, 0  # one bin is kept for the special signature
+    while sig.size > n:
+        if w[0] > mean:
+            out[sig[0]] = bin_no
+            bin_no += 1
+            total -= float(w[0])
+            sig, w = sig[1:], w[1:]
+        else:
+            # first fit over the descending list: a signature is taken iff what the bin holds + its weight stays below max_bin. Taken in runs: from the first one
+            # that fits (the list descends: a binary search), as many consecutive ones as fit (their prefix sums: weights are whole numbers, the sums exact)
+            pre = np.concatenate([[0.0], np.cumsum(w)])
+            desc = -w
+            take = np.zeros(sig.size, dtype=bool)
+            tmp, pos = 0.0, 0
+            while pos < sig.size:
+                j = max(pos, int(np.searchsorted(desc, -(max_bin - tmp), side="right")))  # the first w[j] < max_bin - tmp
+                if j >= sig.size:
+                    break
+                end = int(np.searchsorted(pre, max_bin - tmp + pre[j], side="left")) - 1  # the largest end with tmp + (pre[end] - pre[j]) < max_bin
+                take[j:end] = True
+                tmp += float(pre[end] - pre[j])
+                pos = end
+            out[sig[take]] = bin_no
+            bin_no += 1
+            total -= tmp
+            sig, w = sig[~take], w[~take]
+        n -= 1
+        mean = total / (max_bins - bin_no) if max_bins > bin_no else 0.0
+        max_bin = 1.1 * mean
+    out[sig] = bin_no + np.arange(sig.size, dtype=np.int32)
+    out[size - 1] = bin_no + sig.size
+    if int(out[size - 1]) >= n_bins:  # the reference would write bin n_bins here (groups that stay far below their bound); not met with real statistics
+        raise ValueError(f"balanced_signature_map: the statistics need more than {n_bins} bins")
+    return out
+
+
+def count_stats_sample(ctx, o: dict, part_bytes: int) -> np.ndarray:
+    """stage 0 of `count`: the first part of every input file through a capi.SigStats accumulator -> the statistics, uint32[4^m + 1]"""
+    acc = capi.SigStats(ctx, o["k"], o["m"])
+    try:
+        for path in o["inputs"]:
+            try:
+                part = next(iter(multiline_parts(path, part_bytes) if o["file_type"] == 2 else readsio.parts(path, o["file_type"] == 1, part_bytes)), None)
+            except OSError as e:
+                raise UsageError(f"cannot open file: {path} ({e.strerror})")
+            except readsio.FormatError as e:
+                raise UsageError(f"count: {path}: {e}")
+            if part is None:
+                continue
+            try:
+                acc.part(part, file_type=o["file_type"], flags=capi.SPLIT_HOMOPOLYMER if o["hc"] else 0)
+            except capi.KmcHipError as e:
+                if e.code == capi.UNCOVERED:
+                    raise UsageError(f"count: {path}, part 0: {e}")
+                raise
+        return acc.read()
+    finally:
+        acc.close()
+
+
 def multiline_parts(path: str, part_bytes: int):
     """A multi-line FASTA file in parts as the reference's reader hands them to the splitter (CFastqReader::GetPartFromMultilneFasta, fastq_reader.cpp:399-468): a title
     keeps its line end, the sequence lines lose theirs. Parts are cut in front of a '>' at a line start; a record longer than part_bytes makes its part longer."""
@@ -994,10 +1080,15 @@ def multiline_parts(path: str, part_bytes: int):
         yield strip(rest)
 
 
-def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_MULTIPLIER):
+def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_MULTIPLIER, signature_map="fixed"):
     """`kmc` + `kmc_tools transform sort` on the device: the reads of the input files go through a counting session (capi.CountSession) part by part, the ordered body is
     written as a KMC1 database. Returns dict(stats = the four tallies of stage 2 by name, totals = reads, super-k-mers, k-mers, bytes of bin records, n_records, n_parts,
-    n_segments, n_batches, balance = k-mers of the largest bin / of the mean bin); keep=True: (that dict, the open session, its view) — the caller goes on on the device and closes the session."""
+    n_segments, n_batches, balance = k-mers of the largest bin / of the mean bin, map = the signature map that ran); keep=True: (that dict, the open session, its view) —
+    the caller goes on on the device and closes the session.
+    signature_map: "fixed" = count_signature_map's spread; "stats" = stage 0 first: the first part of every input file through capi.SigStats, the map from
+    balanced_signature_map. With fewer than COUNT_MAP_MIN_BINS bins "stats" keeps the fixed map and the result says so. The database does not depend on the map."""
+    if signature_map not in ("fixed", "stats"):
+        raise ValueError(f'count: signature_map is "fixed" or "stats", not {signature_map!r}')
     o = parse_count(argv)
     if part_bytes is None:
         part_bytes = int(os.environ.get("KMC_HIP_COUNT_PART_MB", "0")) << 20 or COUNT_PART_BYTES
@@ -1007,7 +1098,14 @@ def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_
         ctx = capi.Context((0,))
     ses = None
     try:
-        ses = capi.CountSession(ctx, k, o["m"], o["n_bins"], o["both"], count_signature_map(o["m"], o["n_bins"], map_multiplier))
+        if signature_map == "stats" and o["n_bins"] < COUNT_MAP_MIN_BINS:
+            signature_map = "fixed"
+        if signature_map == "stats":
+            sig_map = balanced_signature_map(count_stats_sample(ctx, o, part_bytes), o["m"], o["n_bins"], capi.allowed_signatures(o["m"], ctx.L))
+            sig_map = np.where(sig_map < 0, o["n_bins"] - 1, sig_map).astype(np.int32)  # no k-mer has a signature that is not allowed; the session takes bins only
+        else:
+            sig_map = count_signature_map(o["m"], o["n_bins"], map_multiplier)
+        ses = capi.CountSession(ctx, k, o["m"], o["n_bins"], o["both"], sig_map)
         p = ses.split_params(file_type=o["file_type"], flags=capi.SPLIT_HOMOPOLYMER if o["hc"] else 0)
         n_parts = 0
         for path in o["inputs"]:
@@ -1039,7 +1137,7 @@ def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_
         dbio.write_kmc1(o["out"], k, view.counter_size, p_out, o["ci"], o["cx"], o["both"], lut, recs)
         res = dict(stats=dict(zip(("n_unique", "n_below_min", "n_above_max", "n_total"), (int(x) for x in st))),
                    totals=dict(zip(("n_reads", "n_superkmers", "n_kmers", "bin_bytes"), (int(x) for x in tot))), n_records=n_records, n_parts=n_parts,
-                   n_segments=info["n_segments"], n_batches=info["n_batches"], balance=info["largest_bin"] * o["n_bins"] / max(int(tot[2]), 1))
+                   n_segments=info["n_segments"], n_batches=info["n_batches"], balance=info["largest_bin"] * o["n_bins"] / max(int(tot[2]), 1), map=signature_map)
         if keep:
             ses_kept, ses = ses, None
             return res, ses_kept, view
@@ -1057,14 +1155,15 @@ def count_report(res: dict) -> str:
     rows = [("No. of k-mers below min. threshold", s["n_below_min"]), ("No. of k-mers above max. threshold", s["n_above_max"]), ("No. of unique k-mers", s["n_unique"]),
             ("No. of unique counted k-mers", s["n_unique"] - s["n_below_min"] - s["n_above_max"]), ("Total no. of k-mers", s["n_total"]), ("Total no. of reads", t["n_reads"]),
             ("Total no. of super-k-mers", t["n_superkmers"])]
-    return "\n".join("   %-35s: %12d" % r for r in rows) + "\n   %-35s: %12.2f  (%d parts, %d segments gathered, %d stage-2 batches)" % (
-        "Largest bin / mean bin (k-mers)", res["balance"], res["n_parts"], res["n_segments"], res["n_batches"])
+    which = {"fixed": "the fixed signature map", "stats": "the map from stage-0 statistics"}[res.get("map", "fixed")]
+    return "\n".join("   %-35s: %12d" % r for r in rows) + "\n   %-35s: %12.2f  (%s; %d parts, %d segments gathered, %d stage-2 batches)" % (
+        "Largest bin / mean bin (k-mers)", res["balance"], which, res["n_parts"], res["n_segments"], res["n_batches"])
 
 
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if argv and argv[0] == "count":
-        print(count_report(count(argv[1:])))
+        print(count_report(count(argv[1:], signature_map="stats" if os.environ.get("KMC_HIP_COUNT_MAP") == "stats" else "fixed")))
         return 0
     if argv and argv[0] == "filter":
         print(", ".join(f"{a} {b}" for a, b in filter_reads(argv[1:]).items()))

@@ -48,10 +48,10 @@ def collect(extra_flags=()):
 def main():
     rows = collect(sys.argv[1:])
     print("# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage kmc_amd/csrc/kmc_hip.hip %s" % " ".join(sys.argv[1:]))
-    print("%-44s %6s %6s %10s %10s %12s %10s" % ("kernel", "VGPRs", "SGPRs", "VGPR spill", "SGPR spill", "scratch B/ln", "waves/SIMD"))
+    print("%-44s %6s %6s %10s %10s %12s %10s %10s" % ("kernel", "VGPRs", "SGPRs", "VGPR spill", "SGPR spill", "scratch B/ln", "waves/SIMD", "LDS B/blk"))
     for r in sorted(rows, key=lambda r: r["name"]):
-        print("%-44s %6d %6d %10d %10d %12d %10d" % (r["name"], r.get("VGPRs", -1), r.get("TotalSGPRs", -1), r.get("VGPRs Spill", -1), r.get("SGPRs Spill", -1),
-                                                      r.get("ScratchSize [bytes/lane]", -1), r.get("Occupancy [waves/SIMD]", -1)))
+        print("%-44s %6d %6d %10d %10d %12d %10d %10d" % (r["name"], r.get("VGPRs", -1), r.get("TotalSGPRs", -1), r.get("VGPRs Spill", -1), r.get("SGPRs Spill", -1),
+                                                          r.get("ScratchSize [bytes/lane]", -1), r.get("Occupancy [waves/SIMD]", -1), r.get("LDS Size [bytes/block]", -1)))
 
 
 if __name__ == "__main__":
