@@ -348,6 +348,34 @@ typedef struct kmc_hip_db_expr_step {
 int kmc_hip_db_expr_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *views, uint32_t n_views, const kmc_hip_db_expr_step *steps, uint32_t n_steps,
                            const kmc_hip_db_op *out, uint8_t *d_out, uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers, uint64_t stats[5]);
 
+/* ---- a KFF file's records as a database body -----------------------------------------------------------
+ * What kmc_tools' KFF readers hand to `simple`, `transform`, `complex` and `filter` (kmc_tools/kff_db_reader.h; the container: kmc_core/kff_writer.cpp,
+ * kmc_tools/kff_info_reader.cpp), on the device: d_kff holds the records of all raw sections of one file back to back, section i the next section_n_recs[i] of them
+ * (a host array; sections may be empty). A record is ceil(kmer_len / 4) bytes of k-mer, most significant first and right-aligned (kmer_len % 4 != 0: the top bits of the
+ * first byte are padding and zero), then data_size counter bytes, MOST significant first (kff_db_reader.h:374-401; `max` = 1, so no per-block count). Every section is
+ * strictly ascending (the file's `ordered` = 1, which kmc_tools requires, kmer_file_header.cpp:143-147). kmer_len 1..224, data_size 1..4, (kmer_len -
+ * out_lut_prefix_len) a positive multiple of 4 and out_lut_prefix_len 1..15. d_out receives n = sum of section_n_recs database records of (kmer_len -
+ * out_lut_prefix_len) / 4 suffix bytes and data_size counter bytes, least significant first, as kmc_hip_db_set_op_device leaves them: the view (d_out, n, d_lut_out,
+ * out_lut_prefix_len, data_size) is what every kmc_hip_db_* entry takes. *n_kmers = n.
+ *   ordered = 1: ONE ascending body, d_lut_out the KMC1 LUT of 4^out_lut_prefix_len entries. At most one section that is not empty: the records are re-framed where they
+ *     lie (k_kff_repack). Several: they are unpacked, sorted by the stable LSD passes kmc_hip_order_database_device uses and packed again; a k-mer that two sections
+ *     hold is KMC_HIP_ECORRUPT (the reference's merge, kff_db_reader.h:929-1112, would emit it twice, and every kmc_hip_db_* entry takes unique k-mers).
+ *   ordered = 0: the body as it lies in the file, d_lut_out the segmented LUT kmc_hip_db_dump_device and kmc_hip_db_histogram_device take with n_lut_segments =
+ *     n_sections: n_sections x 4^out_lut_prefix_len global record offsets and ONE closing entry (= n) behind them (kmc2_db_reader.h:1776-1791) — what `transform`
+ *     histogram and dump without -s read, in file order as the reference's sequential reader (kff_db_reader.h:1320-1492). No sort. With n_sections = 0 the LUT is
+ *     the closing entry alone. n_sections x 4^out_lut_prefix_len + 1 must be below 2^31.
+ * The same pass verifies the records: padding bits zero, the prefix below 4^out_lut_prefix_len (one check: the padding bits are the top bits of the prefix bytes), every
+ * record strictly greater than its predecessor in its section on the big-endian bytes. KMC_HIP_ECORRUPT names the smallest offending record and its section; the
+ * outputs are then undefined and nothing outside them is touched.
+ * KMC_HIP_EINVAL: a NULL argument (d_kff may be NULL when there is no record, section_n_recs when n_sections is 0), data_size outside 1..4, kmer_len 0 or > 224, an
+ * out_lut_prefix_len that is not as above, ordered > 1; KMC_HIP_ECAPACITY: out_capacity (bytes) below n records. Empty input — no section, or only empty ones — is
+ * legal. Synchronous; temporaries are the stream slot's grow-only buffers. $KMC_HIP_KFF_IPT: records per thread of a k_kff_repack tile of 256 threads (default: 32 KiB
+ * of LDS per workgroup, at most 8).
+ * Replaces: CKFFDbReader<SIZE> (kff_db_reader.h), for sorted access a priority-queue merge over all sections on one thread. */
+int kmc_hip_kff_import_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t data_size, const uint8_t *d_kff /* the records of all sections, back to back */,
+                              const uint64_t *section_n_recs /* host, [n_sections] */, uint32_t n_sections, uint32_t ordered, uint32_t out_lut_prefix_len, uint8_t *d_out,
+                              uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers);
+
 /* ---- end-of-run tallies ---------------------------------------------------------------------- */
 
 /* Sum stats[4] over the context's devices with one RCCL all-reduce (ncclUint64 x 4, ncclSum) over xGMI.

@@ -145,7 +145,7 @@ SYMBOLS = [
     "kmc_hip_sigstats_open", "kmc_hip_sigstats_part", "kmc_hip_sigstats_read", "kmc_hip_sigstats_close", "kmc_hip_sigstats_allowed",
     "kmc_hip_db_set_op_device", "kmc_hip_db_query_reads_device",
     "kmc_hip_db_reduce_device", "kmc_hip_db_histogram_device", "kmc_hip_db_dump_device",
-    "kmc_hip_db_expr_device",
+    "kmc_hip_db_expr_device", "kmc_hip_kff_import_device",
     "kmc_hip_count_open", "kmc_hip_count_part", "kmc_hip_count_finish", "kmc_hip_count_order", "kmc_hip_count_info", "kmc_hip_count_timings", "kmc_hip_count_close", "kmc_hip_debug_gather_segments",
 ]
 
@@ -247,6 +247,8 @@ def load():
         L.kmc_hip_db_dump_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, u64p]
     if hasattr(L, "kmc_hip_db_expr_device"):  # added within ABI version 4
         L.kmc_hip_db_expr_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.POINTER(DbExprStep), C.c_uint32, C.POINTER(DbOp), vp, C.c_uint64, vp, u64p, u64p]
+    if hasattr(L, "kmc_hip_kff_import_device"):  # added within ABI version 4
+        L.kmc_hip_kff_import_device.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, u64p]
     bind_count(L)
     _LIB = L
     return L
@@ -570,6 +572,17 @@ class Context:
         n, st = C.c_uint64(), (C.c_uint64 * 5)()
         self._chk(self.L.kmc_hip_db_expr_device(self.h, dev, kmer_len, va, len(views), sa, len(steps), C.byref(out), d_out, out_capacity, d_lut_out, C.byref(n), st))
         return n.value, dict(zip(DBX_STATS, (int(x) for x in st)))
+
+    def kff_import_device(self, kmer_len: int, data_size: int, d_kff: int, section_n_recs, ordered: bool, out_lut_prefix_len: int, d_out: int, out_capacity: int,
+                          d_lut_out: int, dev: int = 0) -> int:
+        """The records of a KFF file's raw sections (d_kff: back to back; section_n_recs: records per section) as a database body (kmc_hip_kff_import_device): ordered, one
+        ascending body under a KMC1 LUT; otherwise the body in file order under the segmented LUT of len(section_n_recs) x 4^p + 1 entries. Returns the number of records."""
+        self._need("kmc_hip_kff_import_device")
+        sec = (C.c_uint64 * max(len(section_n_recs), 1))(*[int(x) for x in section_n_recs])
+        n = C.c_uint64()
+        self._chk(self.L.kmc_hip_kff_import_device(self.h, dev, kmer_len, data_size, d_kff or None, sec, len(section_n_recs), 1 if ordered else 0, out_lut_prefix_len, d_out or None,
+                                                   out_capacity, d_lut_out or None, C.byref(n)))
+        return n.value
 
     def debug_gather_segments(self, d_src: int, d_dst: int, table: np.ndarray, dev: int = 0):
         """test hook: k_cnt_gather on a table of (source offset, destination offset, bytes) triples over two device buffers"""

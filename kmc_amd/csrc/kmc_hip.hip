@@ -33,6 +33,7 @@
 #include "order_db.hip.h"
 #include "stage1_kernels.hip.h"
 #include "count_gather.hip.h"
+#include "kff_db.hip.h"
 
 namespace {
 
@@ -617,3 +618,4 @@ struct DevTemps {
 #include "host_query.hip.h" /* the reads of a file against an ordered database (`kmc_tools filter`) */
 #include "host_transform.hip.h" /* one database reduced, histogrammed or dumped as text (`kmc_tools transform`) */
 #include "host_expr.hip.h" /* a set expression over several ordered databases (`kmc_tools complex`) */
+#include "host_kff.hip.h" /* the records of a KFF file imported as a database body (the KFF inputs of every `kmc_tools` database mode) */

@@ -1,10 +1,12 @@
 """KMC databases on disk <-> numpy: what `python -m kmc_amd.tools` reads and writes.
 
+read_kff() takes a KFF file (kmc_core/kff_writer.cpp) as kmc_tools' CKFFInfoReader does.
 read_database() takes a database as `kmc` writes it (KMC2: records ordered inside every signature bin, kmc_core/kb_completer.cpp:287-320) or as `kmc_tools`
 writes it (KMC1: one ascending sequence, kmc_tools/kmc1_db_writer.h:296-372); the header is parsed as kmc_tools/kmer_file_header.cpp:63-93 does.
 write_kmc1() writes the KMC1 form: markers, LUT, header, records."""
 from __future__ import annotations
 
+import mmap
 import os
 from dataclasses import dataclass, field
 
@@ -38,14 +40,184 @@ class Database:
         return (self.kmer_len - self.lut_prefix_len) // 4 + self.counter_size
 
 
+def kff_path(path: str):
+    """kmc_tools' rule (kmer_file_header.cpp:104-114): the name itself where it is a file, the name + '.kff' only where it is not; None where neither is a file"""
+    if os.path.isfile(path):
+        return path
+    return path + ".kff" if os.path.isfile(path + ".kff") else None
+
+
 def is_kff(path: str) -> bool:
-    """kmc_tools' rule (kmer_file_header.cpp is_kff_file): the name itself, or name + '.kff', is a file that starts with 'KFF'"""
-    for p in (path, path + ".kff"):
-        if os.path.isfile(p):
-            with open(p, "rb") as f:
-                if f.read(3) == b"KFF":
-                    return True
-    return False
+    """the file kff_path() names starts with 'KFF' (kmer_file_header.cpp is_kff_file; the end marker is read_kff's to refuse)"""
+    p = kff_path(path)
+    if p is None:
+        return False
+    with open(p, "rb") as f:
+        return f.read(3) == b"KFF"
+
+
+KFF_ENCODING = 0b00011011  # A, C, G, T = 0, 1, 2, 3: what kmc and kmc_tools write
+KFF_MAX_K = 224
+
+
+@dataclass
+class KffFile:
+    """A KFF file as kmc_tools takes it (kmer_file_header.cpp:128-174): counter_size is the scopes' data_size, min_count / max_count come from the footer (1 and
+    2^32 - 1 without one), both_strands is the `canonical` byte, and total_kmers STAYS 0 — so CKMC1DbWriter::calc_lut_prefix_len (kmc1_db_writer.h:425-456) picks the
+    smallest valid prefix length for a database written from it. The fields a front end reads of a Database have the same names."""
+    path: str  # the file itself (the name given, or the name + '.kff')
+    kmer_len: int
+    counter_size: int
+    min_count: int
+    max_count: int
+    both_strands: bool
+    sections: list  # (file offset of the first record, n_recs) of every raw section in file order, the scopes flattened
+    raw: np.ndarray = None  # the file's bytes: a read-only view of the mapped file, not a copy
+    mode: int = 0
+    total_kmers: int = 0
+    lut_prefix_len: int = 0
+    signature_len: int = 0
+    kmc2: bool = False
+
+    @property
+    def rec_bytes(self) -> int:
+        return (self.kmer_len + 3) // 4 + self.counter_size
+
+    @property
+    def n_recs(self) -> int:
+        return sum(n for _, n in self.sections)
+
+    def records(self) -> np.ndarray:
+        """the records of all sections back to back: what kmc_hip_kff_import_device takes. One section that is not empty: a view of the mapped file, no copy"""
+        rb = self.rec_bytes
+        parts = [self.raw[o:o + n * rb] for o, n in self.sections if n]
+        return parts[0] if len(parts) == 1 else np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+
+
+def read_kff(path: str) -> KffFile:
+    """The container as CKFFInfoReader walks it (kff_info_reader.cpp:26-202): markers, header, footer, the index chain from the footer's first_index (or an index as the
+    first section), then every indexed section in file order. Accepted: raw sections only, every scope ordered = 1, max = 1, one k (<= 224), one data_size in 1..4,
+    all_unique = 1, the encoding kmc writes. Everything else is a DbFormatError that names the cause; no file is read in part."""
+    name = kff_path(path)
+    if name is None:
+        raise DbFormatError(f"{path}: no such KFF file")
+    size = os.path.getsize(name)
+    if size < 15:
+        raise DbFormatError(f"{name}: KFF file refused: truncated ({size} bytes: no room for the header and the KFF marker at the end)")
+    with open(name, "rb") as f:
+        raw = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)  # parsed and handed on where it lies: the file is held once
+    b = np.frombuffer(raw, dtype=np.uint8)
+
+    def bad(why):
+        return DbFormatError(f"{name}: KFF file refused: {why}")
+
+    def be(pos, width=8, what="a field"):
+        if pos < 0 or pos + width > size:
+            raise bad(f"truncated ({what} at byte {pos} lies behind the end of the file)")
+        return int.from_bytes(raw[pos:pos + width], "big")
+
+    def variables(pos, what):
+        """a 'v' section whose type byte is at pos -> dict"""
+        out = {}
+        n_vars = be(pos + 1, 8, what)
+        pos += 9
+        if n_vars > size:
+            raise bad(f"truncated ({what} announces {n_vars} variables)")
+        for _ in range(n_vars):
+            end = raw.find(b"\0", pos)
+            if end < 0:
+                raise bad(f"truncated (a variable name of {what} does not end)")
+            out[raw[pos:end].decode("latin-1")] = be(end + 1, 8, what)
+            pos = end + 9
+        return out
+
+    if raw[:3] != b"KFF":
+        raise bad("no KFF marker at the beginning")
+    if size < 15 or raw[-3:] != b"KFF":
+        raise bad("no KFF marker at the end (a truncated file?)")
+    encoding, all_unique, canonical = raw[5], raw[6], raw[7]
+    if all_unique == 0:
+        raise bad("all_unique = 0: only files of unique k-mers are read, as by kmc_tools")
+    if encoding != KFF_ENCODING:
+        raise bad(f"encoding {encoding:#010b}: only {KFF_ENCODING:#010b} (A, C, G, T = 0, 1, 2, 3) is read")
+    footer = {}
+    if size >= 26 and raw[size - 23:size - 11] == b"footer_size\0":
+        start = size - 3 - be(size - 11)
+        if start < 12 or raw[start:start + 1] != b"v":
+            raise bad("the footer does not start as a 'v' section")
+        footer = variables(start, "the footer")
+    first = 12 + be(8, 4, "the free block's size")
+    if first >= size:
+        raise bad("truncated (the free block reaches behind the end of the file)")
+    index_at = footer.get("first_index")
+    if raw[first:first + 1] == b"i":
+        if index_at is not None and index_at != first:
+            raise bad("the footer's first_index and the index that is the first section are inconsistent")
+        index_at = first
+    if index_at is None:
+        raise bad("no index: no first_index in the footer and the first section is not an index")
+    index, seen = [], set()
+    while index_at:
+        if index_at in seen or index_at >= size or raw[index_at:index_at + 1] != b"i":
+            raise bad(f"missing index (no 'i' section at byte {index_at})")
+        seen.add(index_at)
+        n_entries = be(index_at + 1, 8, "an index")
+        if n_entries > size:
+            raise bad(f"truncated (an index announces {n_entries} sections)")
+        end = index_at + 9 + 9 * n_entries + 8
+        for i in range(n_entries):
+            at = index_at + 9 + 9 * i
+            rel = be(at + 1, 8, "an index")
+            index.append((end + (rel - (1 << 64) if rel >> 63 else rel), raw[at:at + 1]))
+        index_at = be(end - 8, 8, "an index")
+    index.sort()
+    for pos, typ in index:
+        if pos < 0 or pos >= size or raw[pos:pos + 1] != typ:
+            raise bad(f"the index is inconsistent with the file (no '{typ.decode('latin-1')}' section at byte {pos})")
+    scopes = []  # [variables, [(data offset, n_recs)]]
+    for pos, typ in index:
+        if typ == b"i":
+            continue
+        if typ == b"v":
+            if scopes and not scopes[-1][1]:
+                scopes.pop()
+            scopes.append([variables(pos, "a variable section"), []])
+        elif typ == b"r":
+            if not scopes:
+                raise bad("a raw section without a variable section in front")
+            for var in ("k", "max", "data_size"):
+                if var not in scopes[-1][0]:
+                    raise bad(f"`{var}` is not defined for a raw section")
+            scopes[-1][1].append((pos + 9, be(pos + 1, 8, "a raw section")))
+        elif typ == b"m":
+            raise bad("a minimizer ('m') section: only raw sections are read, as by kmc_tools")
+        else:
+            raise bad(f"unsupported section type {typ!r}")
+    scopes = [s for s in scopes if s[1]]
+    if not scopes:
+        raise bad("no scope with a data section was found (is the file fully indexed?)")
+    ks = sorted({s[0]["k"] for s in scopes})
+    if len(ks) != 1:
+        raise bad(f"several k values ({', '.join(map(str, ks))}): only files with one k are read, as by kmc_tools")
+    k = ks[0]
+    if not 1 <= k <= KFF_MAX_K:
+        raise bad(f"k = {k}: 1..{KFF_MAX_K} is read")
+    for v, _ in scopes:
+        if not v.get("ordered", 0):
+            raise bad("ordered = 0: all sections must be ordered, as kmc_tools requires")
+        if v["max"] != 1:
+            raise bad(f"max = {v['max']}: only one k-mer per block is read")
+    sizes = sorted({s[0]["data_size"] for s in scopes})
+    if len(sizes) != 1:
+        raise bad(f"scopes with different data_size ({', '.join(map(str, sizes))})")
+    if not 1 <= sizes[0] <= 4:
+        raise bad(f"data_size {sizes[0]}: counters of 1..4 bytes are read (kmc_tools refuses k-mers without counters)")
+    rb = (k + 3) // 4 + sizes[0]
+    sections = [sec for _, secs in scopes for sec in secs]
+    for off, n in sections:
+        if off + n * rb > size - 3:
+            raise bad(f"truncated (the raw section at byte {off - 9} announces {n} records of {rb} bytes)")
+    return KffFile(name, k, sizes[0], footer.get("min_count", 1), footer.get("max_count", 0xFFFFFFFF), bool(canonical), sections, b)
 
 
 def read_database(path: str) -> Database:

@@ -7,7 +7,9 @@ python -m kmc_amd.tools complex <operations_definition_file>
 the databases, the reads and the text written are byte for byte those kmc_tools writes. simple: one kmc_hip_db_set_op_device call per output. filter: one
 kmc_hip_db_query_reads_device call per part of the reads file. transform: the input uploaded once, then per output kmc_hip_db_reduce_device (reduce, compact, set_counts,
 sort), kmc_hip_db_histogram_device, or kmc_hip_db_dump_device per part of the text. A database as `kmc` wrote it (KMC2) is ordered on the device first — by transform
-only when an output needs the order. complex: every input the expression names uploaded once, then ONE kmc_hip_db_expr_device call for the whole expression."""
+only when an output needs the order. complex: every input the expression names uploaded once, then ONE kmc_hip_db_expr_device call for the whole expression.
+Every <db> may be a KFF file (the name, or the name + '.kff', as kmc_tools takes it): its sections go up in one piece and kmc_hip_kff_import_device makes the body — one
+ascending body where the mode needs the order, the file's own order under a segmented LUT otherwise. The outputs remain KMC databases and text."""
 from __future__ import annotations
 
 import os
@@ -85,16 +87,25 @@ def parse_simple(argv):
 DEFAULT_COUNTER_OP = {"intersect": "min", "union": "sum"}  # config.h:96-110; every other operation: diff
 
 
+def _read_input(path: str):
+    """a database, or a KFF file by kmc_tools' path rule (kmer_file_header.cpp:104-126) -> dbio.Database | dbio.KffFile"""
+    if dbio.is_kff(path) and not os.path.exists(path + ".kmc_pre"):
+        return dbio.read_kff(path)
+    return dbio.read_database(path)
+
+
 class _DeviceDb:
     """an input's KMC1 body in HBM"""
 
-    def __init__(self, ctx, db: dbio.Database, order: bool = True):
-        """order False: a KMC2 body stays as it lies in the file, under the file's LUT of n_seg x 4^p global offsets and the closing entry (what transform's
-        histogram and unordered dump read)"""
+    def __init__(self, ctx, db, order: bool = True):
+        """order False: a KMC2 body, or the sections of a KFF file, stay as they lie in the file, under a LUT of n_seg x 4^p global offsets and the closing entry (what
+        transform's histogram and unordered dump read)"""
         self.ctx, self.db = ctx, db
         self.allocs = []
         self.n_seg = 1
-        if db.kmc2 and order:
+        if isinstance(db, dbio.KffFile):
+            self._import_kff(db, order)
+        elif db.kmc2 and order:
             self._order(db)
         elif db.kmc2:
             self.p, self.n, self.n_seg = db.lut_prefix_len, db.total_kmers, (db.raw_lut.size - 1) >> (2 * db.lut_prefix_len)
@@ -109,6 +120,25 @@ class _DeviceDb:
         if a.nbytes:
             self.ctx.h2d(d, np.ascontiguousarray(a))
         return d
+
+    def _import_kff(self, db, order):
+        """the sections' records up back to back in one piece; ordered: one ascending body for the prefix length of its size; otherwise the file's order, the smallest
+        valid prefix length and one LUT segment per section"""
+        ctx, k = self.ctx, db.kmer_len
+        sec_n = [n for _, n in db.sections] or [0]
+        n = sum(sec_n)
+        self.p = dbio.best_lut_prefix_len(k, n if order else 0)
+        self.n_seg = 1 if order else len(sec_n)
+        rb = (k - self.p) // 4 + db.counter_size
+        d_kff = ctx.malloc(n * db.rec_bytes + 256)
+        try:
+            if n:
+                ctx.h2d(d_kff, db.records())
+            self.d_recs, self.d_lut = ctx.malloc(n * rb + 256), ctx.malloc(8 * ((self.n_seg << (2 * self.p)) + 1))
+            self.allocs += [self.d_recs, self.d_lut]
+            self.n = ctx.kff_import_device(k, db.counter_size, d_kff, sec_n, order, self.p, self.d_recs, n * rb, self.d_lut)
+        finally:
+            ctx.free(d_kff)
 
     def _order(self, db):
         ctx = self.ctx
@@ -141,7 +171,7 @@ def simple(argv, ctx=None) -> list:
     dbs = []
     for path, _, _ in inputs:
         try:
-            dbs.append(dbio.read_database(path))
+            dbs.append(_read_input(path))
         except dbio.DbFormatError as e:
             raise UsageError(str(e))
     if dbs[0].kmer_len != dbs[1].kmer_len:
@@ -154,7 +184,7 @@ def simple(argv, ctx=None) -> list:
     eff = [(ci or db.min_count, cx or db.max_count) for (_, ci, cx), db in zip(inputs, dbs)]
     def_ci, def_cx = min(e[0] for e in eff), max(e[1] for e in eff)
     def_cs = (1 << (8 * max(db.counter_size for db in dbs))) - 1
-    p_out = max(dbio.best_lut_prefix_len(k, db.total_kmers) for db in dbs)  # kmc1_db_writer.h:425-456
+    p_out = max(dbio.best_lut_prefix_len(k, db.total_kmers) for db in dbs)  # kmc1_db_writer.h:425-456; a KFF input's total_kmers is 0
     canonical = all(db.both_strands for db in dbs)
     own = ctx is None
     if own:
@@ -193,7 +223,7 @@ def simple(argv, ctx=None) -> list:
 
 
 FILTER_USAGE = """usage: python -m kmc_amd.tools filter [-t | -hm] <db> [-ci<v> -cx<v>] <reads> [-ci<v> -cx<v> -fa|-fq] <out> [-fa|-fq]
-  <db>     -ci / -cx: k-mers with a counter outside [ci, cx] count as absent (default: the database's own cutoffs)
+  <db>     a KMC database or a KFF file; -ci / -cx: k-mers with a counter outside [ci, cx] count as absent (default: the database's own cutoffs)
   <reads>  a FASTQ (default, -fq) or FASTA (-fa) file, '.gz' or not, or @file with one file name per line;
            -ci / -cx: keep a read with ci <= k-mers found <= cx (defaults 2 and 1e9); with a '.' in the value a fraction [0, 1] of the read's k-mers (both or neither)
   -t       trim a read behind its last k-mer in front of the first one found fewer than -ci times; -hm: replace every base of such a k-mer by N
@@ -284,7 +314,7 @@ def parse_filter(argv):
             if not o["in_fastq"] and o["out_fastq"]:
                 raise UsageError("cannot set -fq for output when -fa is set for input")
         elif a.startswith("-o"):
-            raise UsageError(f"{a}: KFF is not read or written, only KMC databases")
+            raise UsageError(f"{a}: filter writes reads; neither a KMC database nor KFF is written")
         else:
             raise UsageError(f"Unknown parameter: {a}")
         pos += 1
@@ -364,10 +394,8 @@ def _filter_part(ctx, view, k, both, o, text) -> tuple:
 def filter_reads(argv, ctx=None) -> dict:
     """Runs the command line; returns dict(n_reads, n_written, and the summed tallies of kmc_hip_db_query_reads_device)."""
     o = parse_filter(argv)
-    if dbio.is_kff(o["db"]) and not os.path.exists(o["db"] + ".kmc_pre"):
-        raise UsageError(f"{o['db']}: a KFF file; only KMC databases are read")
     try:
-        db = dbio.read_database(o["db"])
+        db = _read_input(o["db"])
     except (dbio.DbFormatError, OSError) as e:
         raise UsageError(str(e))
     if db.counter_size == 0:
@@ -408,7 +436,7 @@ def filter_reads(argv, ctx=None) -> dict:
 
 
 TRANSFORM_USAGE = """usage: python -m kmc_amd.tools transform <db> [-ci<v> -cx<v>] <oper> [-s] <out> [-ci<v> -cx<v> -cs<v> -okmc] [<oper> ...]
-  <db>     -ci / -cx: k-mers with a counter outside [ci, cx] are absent for every output (default: the database's own cutoffs)
+  <db>     a KMC database or a KFF file (KFF is read, not written); -ci / -cx: k-mers with a counter outside [ci, cx] are absent for every output (default: the database's own cutoffs)
   <oper>   sort | reduce | compact | set_counts <value>  write a KMC database <out> (-ci -cx: drop counters outside; -cs: clamp; compact stores counter 1)
            histogram  writes `counter<TAB>k-mers` for every counter in [-ci, -cx] (default -cx: the smallest of the database's, 10000 and what its counter bytes hold)
            dump [-s]  writes `k-mer<TAB>counter` per k-mer; -s, or any database output on the command line: in ascending k-mer order, otherwise in the input's order
@@ -569,15 +597,13 @@ def _transform_dump(ctx, dev, view, db, r) -> dict:
 def transform(argv, ctx=None) -> list:
     """Runs the command line; returns per output that is written the dict of tallies of its device call(s) (a dump: summed over its parts, with n_bytes)."""
     (path, ci, cx), outputs = parse_transform(argv)
-    if dbio.is_kff(path) and not os.path.exists(path + ".kmc_pre"):
-        raise UsageError(f"{path}: a KFF file; only KMC databases are read")
     try:
-        db = dbio.read_database(path)
+        db = _read_input(path)
     except (dbio.DbFormatError, OSError) as e:
         raise UsageError(str(e))
     if db.counter_size == 0:
         raise UsageError(f"{path}: counter size 0 (a k-mer set without counters) is not supported, as in kmc_tools")
-    if not db.kmc2 and any(o["op"] == "sort" for o in outputs):  # kmc_tools.cpp:421-437
+    if not db.kmc2 and not isinstance(db, dbio.KffFile) and any(o["op"] == "sort" for o in outputs):  # kmc_tools.cpp:421-437: only a KMC1 input is sorted already
         print("Warning: input database is already sorted. Each sort operation will be omitted", file=sys.stderr)
         outputs = [o for o in outputs if o["op"] != "sort"]
         if not outputs:
@@ -611,7 +637,7 @@ def transform(argv, ctx=None) -> list:
 COMPLEX_USAGE = """usage: python -m kmc_amd.tools complex <operations_definition_file>
   the file (kmc_tools' format):
     INPUT:
-    <name> = <db> [-ci<v>] [-cx<v>]     one line per input database; -ci / -cx: k-mers with a counter outside [ci, cx] count as absent
+    <name> = <db> [-ci<v>] [-cx<v>]     one line per input, a KMC database or a KFF file; -ci / -cx: k-mers with a counter outside [ci, cx] count as absent
     ...
     OUTPUT:
     <out> = <expression>                 over the names: + union, * intersect (binds tighter), - kmers_subtract, ~ counters_subtract, parentheses; left to right.
@@ -844,9 +870,8 @@ def complex(argv, ctx=None) -> dict:  # noqa: A001 (the mode's name)
     dbs = []
     for i, (_, path, _, _) in enumerate(o["inputs"]):
         try:
-            if dbio.is_kff(path) and not os.path.exists(path + ".kmc_pre"):
-                raise UsageError(f"{path}: a KFF file; only KMC databases are read")
-            dbs.append(dbio.read_database(path) if i in used else _read_header(path))  # an input that is defined but not used: its header only
+            kff = dbio.is_kff(path) and not os.path.exists(path + ".kmc_pre")
+            dbs.append(_read_input(path) if i in used or kff else _read_header(path))  # a database that is defined but not used: its header only
         except (dbio.DbFormatError, OSError) as e:
             raise UsageError(str(e))
     r = resolve_complex(o, dbs)
