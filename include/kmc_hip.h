@@ -376,6 +376,32 @@ int kmc_hip_kff_import_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint
                               const uint64_t *section_n_recs /* host, [n_sections] */, uint32_t n_sections, uint32_t ordered, uint32_t out_lut_prefix_len, uint8_t *d_out,
                               uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers);
 
+/* ---- two ordered databases compared --------------------------------------------------------------------
+ * `kmc_tools compare <db1> <db2>` on the device: a and b are ordered bodies as every kmc_hip_db_* entry takes them, of one kmer_len (<= 224); lut_prefix_len,
+ * counter_size and cutoffs may differ. Semantics, the reference's: a record whose counter lies outside its view's [cutoff_min, cutoff_max] is absent
+ * (kmc1_db_reader.h:574-576,618); the two sequences of present (k-mer, counter) pairs are walked in step; at the first ordinal i where they disagree the databases
+ * differ — the COUNTER is compared before the k-mer (CComparer::Equals, operations.h:266-285) — and they differ as well where one sequence ends first (:286-292:
+ * `one of input is not finished`). result[8]:
+ *   [KIND]     KMC_HIP_DBC_EQUAL, _COUNTER (the counters at i differ, whatever the k-mers do), _KMER (equal counters, other k-mers), _A_ENDED, _B_ENDED
+ *   [ORDINAL]  i among the present records; min(present A, present B) where one input ended; 0 for EQUAL
+ *   [N_A], [N_B]            present records of a and of b
+ *   [COUNTER_A], [COUNTER_B] the counters at i; 0 for an input that has no record i, and for EQUAL
+ *   [RECORD_A], [RECORD_B]   the numbers in the bodies (cut records included) of the two records at i, for kmc_hip_db_dump_device; n_recs for an input that has no record
+ *                            i; 0 for EQUAL
+ * Both bodies are unpacked to (k-mer words, count word); an input whose cutoffs removed a record is made dense by the stable compaction of kmc_hip_db_reduce_device,
+ * an input that lost nothing is not; k_db_compare walks min(present A, present B) x (words + 1) 64-bit words flat, one word per thread and step, and publishes the
+ * smallest differing record of a wave with one atomic minimum; the waves of a tile that starts behind the published minimum's tile leave at once (a relaxed load: no spin, no ticket).
+ * Which of the two kinds the record at the minimum is, is read from the two records afterwards. The result does not depend on the order in which tiles run.
+ * Synchronous. Either input may be empty (d_recs may then be NULL). KMC_HIP_EINVAL and KMC_HIP_ECORRUPT exactly where kmc_hip_db_set_op_device returns them for its
+ * inputs. Nothing but temporaries of the call is allocated.
+ * $KMC_HIP_COMPARE_STEPS: words per thread of a tile of 256 threads (a power of two, default 8); $KMC_HIP_COMPARE_REVERSED=1: the workgroups take the tiles last to
+ * first (tests: the smaller of two differences must win in either order).
+ * Replaces: CComparer<SIZE>::Equals over two CBundle readers (kmc_tools.cpp:503-528, operations.h:258-295), one thread and two priority-queue readers. */
+enum { KMC_HIP_DBC_EQUAL = 0, KMC_HIP_DBC_COUNTER = 1, KMC_HIP_DBC_KMER = 2, KMC_HIP_DBC_A_ENDED = 3, KMC_HIP_DBC_B_ENDED = 4 };
+enum { KMC_HIP_DBC_RES_KIND = 0, KMC_HIP_DBC_RES_ORDINAL = 1, KMC_HIP_DBC_RES_N_A = 2, KMC_HIP_DBC_RES_N_B = 3, KMC_HIP_DBC_RES_COUNTER_A = 4, KMC_HIP_DBC_RES_COUNTER_B = 5,
+       KMC_HIP_DBC_RES_RECORD_A = 6, KMC_HIP_DBC_RES_RECORD_B = 7 };
+int kmc_hip_db_compare_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *a, const kmc_hip_db_view *b, uint64_t result[8]);
+
 /* ---- end-of-run tallies ---------------------------------------------------------------------- */
 
 /* Sum stats[4] over the context's devices with one RCCL all-reduce (ncclUint64 x 4, ncclSum) over xGMI.

@@ -119,6 +119,8 @@ DB_STATS = ("n_pairs", "n_only_a", "n_only_b", "n_below_min", "n_above_max", "n_
 DBQ_STATS = ("n_valid_windows", "n_found", "n_cut", "n_invalid_windows")  # stats[] of kmc_hip_db_query_reads_device, in order
 DBT_STATS = ("n_cut_in", "n_below_min", "n_above_max", "n_written")  # stats[] of kmc_hip_db_reduce_device and kmc_hip_db_dump_device, in order
 DBH_STATS = ("n_cut_in", "n_outside", "n_counted")  # stats[] of kmc_hip_db_histogram_device, in order
+DBC_RESULT = ("kind", "ordinal", "n_a", "n_b", "counter_a", "counter_b", "record_a", "record_b")  # result[] of kmc_hip_db_compare_device, in order
+DBC_KINDS = ("equal", "counter", "kmer", "a_ended", "b_ended")  # KMC_HIP_DBC_*: result[0]
 DBX_STATS = ("n_keys", "n_result", "n_below_min", "n_above_max", "n_written")  # stats[] of kmc_hip_db_expr_device, in order
 
 
@@ -145,7 +147,7 @@ SYMBOLS = [
     "kmc_hip_sigstats_open", "kmc_hip_sigstats_part", "kmc_hip_sigstats_read", "kmc_hip_sigstats_close", "kmc_hip_sigstats_allowed",
     "kmc_hip_db_set_op_device", "kmc_hip_db_query_reads_device",
     "kmc_hip_db_reduce_device", "kmc_hip_db_histogram_device", "kmc_hip_db_dump_device",
-    "kmc_hip_db_expr_device", "kmc_hip_kff_import_device",
+    "kmc_hip_db_expr_device", "kmc_hip_kff_import_device", "kmc_hip_db_compare_device",
     "kmc_hip_count_open", "kmc_hip_count_part", "kmc_hip_count_finish", "kmc_hip_count_order", "kmc_hip_count_info", "kmc_hip_count_timings", "kmc_hip_count_close", "kmc_hip_debug_gather_segments",
 ]
 
@@ -247,6 +249,8 @@ def load():
         L.kmc_hip_db_dump_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, vp, C.c_uint64, u64p, u64p]
     if hasattr(L, "kmc_hip_db_expr_device"):  # added within ABI version 4
         L.kmc_hip_db_expr_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.POINTER(DbExprStep), C.c_uint32, C.POINTER(DbOp), vp, C.c_uint64, vp, u64p, u64p]
+    if hasattr(L, "kmc_hip_db_compare_device"):  # added within ABI version 4
+        L.kmc_hip_db_compare_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.POINTER(DbView), u64p]
     if hasattr(L, "kmc_hip_kff_import_device"):  # added within ABI version 4
         L.kmc_hip_kff_import_device.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, u64p]
     bind_count(L)
@@ -563,6 +567,13 @@ class Context:
         self._chk(self.L.kmc_hip_db_dump_device(self.h, dev, kmer_len, C.byref(db), n_lut_segments, first, count, cutoff_min, cutoff_max, counter_max, d_text or None, text_capacity,
                                                 C.byref(n), st))
         return n.value, dict(zip(DBT_STATS, (int(x) for x in st)))
+
+    def db_compare_device(self, kmer_len: int, a: DbView, b: DbView, dev: int = 0) -> dict:
+        """`kmc_tools compare` between two device-resident KMC1 bodies (kmc_hip_db_compare_device); returns the dict of DBC_RESULT (kind: an index into DBC_KINDS)."""
+        self._need("kmc_hip_db_compare_device")
+        res = (C.c_uint64 * 8)()
+        self._chk(self.L.kmc_hip_db_compare_device(self.h, dev, kmer_len, C.byref(a), C.byref(b), res))
+        return dict(zip(DBC_RESULT, (int(x) for x in res)))
 
     def db_expr_device(self, kmer_len: int, views, steps, out: DbOp, d_out: int, out_capacity: int, d_lut_out: int, dev: int = 0):
         """One `kmc_tools complex` expression over device-resident KMC1 bodies (kmc_hip_db_expr_device). views: DbView's; steps: the postfix program as (kind, arg) pairs

@@ -618,4 +618,5 @@ struct DevTemps {
 #include "host_query.hip.h" /* the reads of a file against an ordered database (`kmc_tools filter`) */
 #include "host_transform.hip.h" /* one database reduced, histogrammed or dumped as text (`kmc_tools transform`) */
 #include "host_expr.hip.h" /* a set expression over several ordered databases (`kmc_tools complex`) */
+#include "host_compare.hip.h" /* two ordered databases compared (`kmc_tools compare`) */
 #include "host_kff.hip.h" /* the records of a KFF file imported as a database body (the KFF inputs of every `kmc_tools` database mode) */

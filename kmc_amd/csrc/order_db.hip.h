@@ -1168,4 +1168,124 @@ __global__ void __launch_bounds__(CX_THREADS) k_cx_tile(CxLeaves lv, CxProg pg, 
 	}
 }
 
+/* ---- two ordered databases compared (`kmc_tools compare`) ----
+ * Both bodies through k_db_unpack (every record present), k_tr_compact<false> counts what each input's cutoffs remove; an input that lost records is made dense by
+ * k_db_cumsum and k_tr_compact<true>, an input that lost nothing is dense already. Then
+ *   k_db_compare         flat over the min(na, nb) x (SIZE + 1) words of the two dense arrays: the smallest record that holds a differing word, by one atomicMin per
+ *                        wave that saw one
+ *   k_db_compare_finish  one workgroup: the kind of the difference from the two records at the minimum (the counter first, CComparer::Equals), the counters, and the
+ *                        records' numbers in the bodies (the compaction's tile sums, then one scan over the tile's 256 records) */
+#ifndef DC_THREADS
+#define DC_THREADS 256 /* threads of a k_db_compare workgroup */
+#endif
+constexpr u32 DC_STEPS_LOG2 = 3;     /* words per thread of a tile, log2: 2048 words = 16 KiB of either input per workgroup */
+constexpr u32 DC_STEPS_LOG2_MAX = 8;
+constexpr u64 DC_NONE = ~0ull;       /* no difference seen */
+enum : u32 { DC_EQUAL = 0, DC_COUNTER = 1, DC_KMER = 2, DC_A_ENDED = 3, DC_B_ENDED = 4 };
+
+/* first: DC_NONE before the launch, the smallest record index with a differing word after it. A tile is 2^tile_shift words. A wave whose tile starts behind the
+ * tile in which the published minimum's record starts leaves at once (the value lane 0 read, for the whole wave): every record with a word in it is larger (a record that straddles into the minimum's own tile
+ * from the one before starts there, and may be smaller: that tile is walked). Wave-level operations stand outside the loop: its trip count differs between lanes. */
+template <int SIZE>
+__global__ void __launch_bounds__(DC_THREADS) k_db_compare(const u64 *__restrict__ a, const u64 *__restrict__ b, u64 n_words, u32 tile_shift, u32 reversed, u64 *__restrict__ first)
+{
+	constexpr u64 W = SIZE + 1;
+	const u64 tile = reversed ? (u64)(gridDim.x - 1 - blockIdx.x) : (u64)blockIdx.x;
+	const u64 seen = __shfl(ld_agent(first), 0); /* one value per wave: its lanes leave together or stay together for the ballot and the shuffles below */
+	if (seen != DC_NONE && ((seen * W) >> tile_shift) < tile)
+		return;
+	const u64 w0 = tile << tile_shift, w1 = w0 + (1ull << tile_shift) < n_words ? w0 + (1ull << tile_shift) : n_words;
+	u64 mine = DC_NONE;
+#pragma unroll 4
+	for (u64 w = w0 + threadIdx.x; w < w1; w += DC_THREADS) {
+		const u64 x = a[w], y = b[w];
+		if (x != y && mine == DC_NONE)
+			mine = w; /* ascending: a thread's first is its smallest */
+	}
+	if (__ballot(mine != DC_NONE) == 0)
+		return;
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) {
+		const u64 t = __shfl_down(mine, o);
+		mine = t < mine ? t : mine;
+	}
+	if ((threadIdx.x & 63) == 0)
+		atomicMin((unsigned long long *)first, (unsigned long long)(mine / W));
+}
+
+struct DcInput {
+	const u64 *dense;     /* [n][SIZE + 1]: the present records */
+	u64 n;
+	const u64 *body;      /* [n_body][SIZE + 1]: every record of the body, as k_db_unpack left it */
+	u64 n_body;
+	const u64 *tile_base; /* nullptr: nothing was cut, dense is body; otherwise the present records in front of every tile of TR_THREADS x TR_REDUCE_IPT records [n_tiles + 1] */
+	u64 n_tiles;
+	u32 cut_min;
+	u64 cut_max;
+};
+
+/* the number in the body of the present record `i` (all threads of the workgroup call; the answer lands in *s_rec) */
+template <int SIZE> __device__ __forceinline__ void dc_locate(const DcInput &in, u64 i, bool any, u32 *s_scan, u64 *s_rec)
+{
+	constexpr u64 W = SIZE + 1;
+	if (!any || i >= in.n || !in.tile_base) {
+		if (threadIdx.x == 0)
+			*s_rec = !any ? 0 : i >= in.n ? in.n_body : i;
+		return;
+	}
+	u64 lo = 0, hi = in.n_tiles; /* the last tile with tile_base[t] <= i holds record i (tiles in front of it with the same sum keep nothing; tile_base[n_tiles] = n > i) */
+	while (hi - lo > 1) {
+		const u64 mid = (lo + hi) >> 1;
+		if (in.tile_base[mid] <= i)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	const u64 r = lo * (TR_THREADS * TR_REDUCE_IPT) + threadIdx.x;
+	u32 present = 0;
+	if (threadIdx.x < TR_THREADS * TR_REDUCE_IPT && r < in.n_body) {
+		const u32 c = (u32)in.body[r * W + SIZE];
+		present = c >= in.cut_min && (u64)c <= in.cut_max;
+	}
+	u32 total;
+	const u32 before = block_excl_sum<TR_THREADS / 64, u32>(present, s_scan, total);
+	if (present && in.tile_base[lo] + before == i)
+		*s_rec = r;
+}
+
+template <int SIZE> __global__ void __launch_bounds__(TR_THREADS) k_db_compare_finish(DcInput A, DcInput B, const u64 *__restrict__ first, u64 *__restrict__ result /* [8] */)
+{
+	static_assert(TR_REDUCE_IPT == 1, "dc_locate scans one record per thread");
+	constexpr u64 W = SIZE + 1;
+	__shared__ u32 s_scan[TR_THREADS / 64 + 1];
+	__shared__ u64 s_rec[2];
+	const u64 f = *first, n = A.n < B.n ? A.n : B.n;
+	u32 kind;
+	u64 i;
+	if (f != DC_NONE) {
+		i = f;
+		kind = A.dense[i * W + SIZE] != B.dense[i * W + SIZE] ? DC_COUNTER : DC_KMER;
+	} else if (A.n == B.n) {
+		i = 0;
+		kind = DC_EQUAL;
+	} else {
+		i = n;
+		kind = A.n < B.n ? DC_A_ENDED : DC_B_ENDED;
+	}
+	dc_locate<SIZE>(A, i, kind != DC_EQUAL, s_scan, s_rec);
+	__syncthreads();
+	dc_locate<SIZE>(B, i, kind != DC_EQUAL, s_scan, s_rec + 1);
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		result[0] = kind;
+		result[1] = i;
+		result[2] = A.n;
+		result[3] = B.n;
+		result[4] = kind != DC_EQUAL && i < A.n ? A.dense[i * W + SIZE] : 0;
+		result[5] = kind != DC_EQUAL && i < B.n ? B.dense[i * W + SIZE] : 0;
+		result[6] = s_rec[0];
+		result[7] = s_rec[1];
+	}
+}
+
 #endif

@@ -78,6 +78,11 @@ class KffFile:
     lut_prefix_len: int = 0
     signature_len: int = 0
     kmc2: bool = False
+    # what `kmc_tools info` prints beyond the fields above (kmc_tools.cpp:157-216)
+    scopes: list = field(default_factory=list)  # per scope with a data section, in file order: (its variables as a dict, [(file offset of the first record, n_recs)])
+    encoding: int = 0b00011011  # KFF_ENCODING
+    all_unique: int = 1
+    footer: dict = field(default_factory=dict)  # the footer's variables by name
 
     @property
     def rec_bytes(self) -> int:
@@ -217,7 +222,8 @@ def read_kff(path: str) -> KffFile:
     for off, n in sections:
         if off + n * rb > size - 3:
             raise bad(f"truncated (the raw section at byte {off - 9} announces {n} records of {rb} bytes)")
-    return KffFile(name, k, sizes[0], footer.get("min_count", 1), footer.get("max_count", 0xFFFFFFFF), bool(canonical), sections, b)
+    return KffFile(name, k, sizes[0], footer.get("min_count", 1), footer.get("max_count", 0xFFFFFFFF), bool(canonical), sections, b,
+                   scopes=[(dict(v), list(secs)) for v, secs in scopes], encoding=encoding, all_unique=all_unique, footer=dict(footer))
 
 
 def read_database(path: str) -> Database:

@@ -2,6 +2,9 @@
 python -m kmc_amd.tools filter [-t | -hm] <db> [-ci<v> -cx<v>] <reads> [-ci<v> -cx<v> -fa|-fq] <out> [-fa|-fq]
 python -m kmc_amd.tools transform <db> [-ci<v> -cx<v>] <oper> [-s] <out> [-ci<v> -cx<v> -cs<v> -okmc] [<oper> ...]
 python -m kmc_amd.tools complex <operations_definition_file>
+python -m kmc_amd.tools compare <db1> [-ci<v> -cx<v>] <db2> [-ci<v> -cx<v>]
+python -m kmc_amd.tools check <db> [-ci<v> -cx<v>] <kmer>
+python -m kmc_amd.tools info <db>
 
 `kmc_tools simple`, `kmc_tools filter`, `kmc_tools transform` and `kmc_tools complex` on the device: the argument order and the defaults are the reference's (kmc_tools/parameters_parser.cpp),
 the databases, the reads and the text written are byte for byte those kmc_tools writes. simple: one kmc_hip_db_set_op_device call per output. filter: one
@@ -9,7 +12,10 @@ kmc_hip_db_query_reads_device call per part of the reads file. transform: the in
 sort), kmc_hip_db_histogram_device, or kmc_hip_db_dump_device per part of the text. A database as `kmc` wrote it (KMC2) is ordered on the device first — by transform
 only when an output needs the order. complex: every input the expression names uploaded once, then ONE kmc_hip_db_expr_device call for the whole expression.
 Every <db> may be a KFF file (the name, or the name + '.kff', as kmc_tools takes it): its sections go up in one piece and kmc_hip_kff_import_device makes the body — one
-ascending body where the mode needs the order, the file's own order under a segmented LUT otherwise. The outputs remain KMC databases and text."""
+ascending body where the mode needs the order, the file's own order under a segmented LUT otherwise. The outputs remain KMC databases and text.
+compare: ONE kmc_hip_db_compare_device call on the two ordered bodies; it prints what kmc_tools prints and exits with its status. check: the k-mer as a line of a reads
+buffer through kmc_hip_db_query_reads_device (check_kmers: a batch of them), kmc_tools' presence rule of this mode applied on the host. info: the headers as kmc_tools
+prints them; no device is opened. With these the front end has every mode of the kmc_tools command line."""
 from __future__ import annotations
 
 import os
@@ -908,6 +914,240 @@ def complex(argv, ctx=None) -> dict:  # noqa: A001 (the mode's name)
     return st
 
 
+COMPARE_USAGE = """usage: python -m kmc_amd.tools compare <db1> [-ci<v> -cx<v>] <db2> [-ci<v> -cx<v>]
+  prints `DB Equals` (exit status 0) or `DB Differs` (1): the k-mers of each input whose counter lies in its [-ci, -cx] (default: the database's own cutoffs), walked in
+  ascending order, must agree pair by pair in counter and k-mer; `one of input is not finished` in front where one input ends first"""
+CHECK_USAGE = """usage: python -m kmc_amd.tools check <db> [-ci<v> -cx<v>] <kmer>
+  prints the counter of <kmer> in <db>, 0 where it is absent or its counter is below -ci or NOT BELOW -cx (kmc_tools' rule for this mode); the k-mer is looked up as
+  given, not its canonical form. A KFF file that does not hold it prints nothing"""
+INFO_USAGE = """usage: python -m kmc_amd.tools info <db>
+  prints the header of a KMC database, or the encoding, the scopes and the data sections of a KFF file, as kmc_tools does (headers only: no device is opened)"""
+
+
+class RefError(UsageError):
+    """an error kmc_tools itself reports: its own words on stderr, exit status 1"""
+
+    def __init__(self, msg):
+        SystemExit.__init__(self, msg)
+
+
+def _input_desc(argv, pos):
+    """parameters_parser.cpp:238-270 read_input_desc -> (path, ci, cx, pos); None = not given: up to two of -ci / -cx behind the name"""
+    if pos >= len(argv):
+        raise UsageError("Input database source missed")
+    if argv[pos].startswith("-"):
+        raise UsageError(f"Input database source required, but {argv[pos]}found")
+    path, ci, cx = argv[pos], None, None
+    pos += 1
+    for _ in range(2):
+        if pos >= len(argv) or not argv[pos].startswith("-"):
+            break
+        if argv[pos].startswith("-ci"):
+            ci = _num1(argv[pos], "-ci")
+        elif argv[pos].startswith("-cx"):
+            cx = _num1(argv[pos], "-cx")
+        else:
+            raise UsageError(f"Unknow parameter: {argv[pos]}")
+        pos += 1
+    return path, ci, cx, pos
+
+
+def _validated_inputs(descs):
+    """parameters_parser.cpp:752-795,842-848 validate_input_dbs -> [(db, ci, cx)] with the cutoffs' defaults from the headers"""
+    dbs = []
+    for path, _, _ in descs:
+        try:
+            dbs.append(_read_input(path))
+        except (dbio.DbFormatError, OSError) as e:
+            raise UsageError(str(e))
+    if dbs[0].mode == 1:
+        raise UsageError("quality counters are not supported in kmc tools")
+    for (path, _, _), db in zip(descs[1:], dbs[1:]):
+        if db.mode != dbs[0].mode:
+            raise UsageError("quality/direct based counters conflict!")
+        if db.kmer_len != dbs[0].kmer_len:
+            raise UsageError(f"Database {descs[0][0]} contains {dbs[0].kmer_len}-mers, but database {path} contains {db.kmer_len}-mers")
+    for (path, _, _), db in zip(descs, dbs):
+        if db.counter_size == 0:
+            raise UsageError(f"{path}: counter size 0 (a k-mer set without counters) is not supported, as in kmc_tools")
+    return [(db, ci or db.min_count, cx or db.max_count) for (_, ci, cx), db in zip(descs, dbs)]
+
+
+def parse_compare(argv):
+    """-> [(path, ci, cx)] x 2; None = not given (parameters_parser.cpp:709-713)"""
+    if not argv:
+        raise UsageError(COMPARE_USAGE)
+    a = _input_desc(argv, 0)
+    b = _input_desc(argv, a[3])
+    if b[3] < len(argv):
+        raise UsageError(f"Unknow parameter: {argv[b[3]]}\n" + COMPARE_USAGE)
+    return [a[:3], b[:3]]
+
+
+def _dump_one(ctx, dev, k, record) -> str:
+    """the k-mer of one record of a body as text: a one-record kmc_hip_db_dump_device with the cutoffs wide open"""
+    d_text = ctx.malloc(k + 12 + 256)
+    try:
+        n_bytes, _ = ctx.db_dump_device(k, dev.view(0, U32_MAX), dev.n_seg, record, 1, 1, U32_MAX, U32_MAX, d_text, k + 12)
+        text = np.zeros(n_bytes, dtype=np.uint8)
+        if n_bytes:
+            ctx.d2h(text, d_text)
+    finally:
+        ctx.free(d_text)
+    return text.tobytes().decode().split("\t")[0]
+
+
+def compare(argv, ctx=None) -> dict:
+    """Runs the command line; returns result[] of kmc_hip_db_compare_device as a dict (capi.DBC_RESULT; kind by its name in capi.DBC_KINDS) and, where the inputs
+    differ, kmer_a / kmer_b: the text of the two k-mers at the first difference (None for an input that ended)."""
+    ins = _validated_inputs(parse_compare(argv))
+    k = ins[0][0].kmer_len
+    own = ctx is None
+    if own:
+        ctx = capi.Context((0,))
+    dev = []
+    try:
+        dev = [_DeviceDb(ctx, db, order=True) for db, _, _ in ins]
+        res = ctx.db_compare_device(k, *(d.view(ci, cx) for d, (_, ci, cx) in zip(dev, ins)))
+        res["kind"] = capi.DBC_KINDS[res["kind"]]
+        if res["kind"] != "equal":
+            for q, d in zip("ab", dev):
+                res["kmer_" + q] = _dump_one(ctx, d, k, res["record_" + q]) if res["record_" + q] < d.n else None
+    finally:
+        for d in dev:
+            d.free()
+        if own:
+            ctx.close()
+    return res
+
+
+def compare_report(res: dict) -> str:
+    """what kmc_tools prints (operations.h:288, kmc_tools.cpp:518-527)"""
+    if res["kind"] == "equal":
+        return "DB Equals\n"
+    return ("one of input is not finished\n" if res["kind"] in ("a_ended", "b_ended") else "") + "DB Differs\n"
+
+
+CHECK_PART_KMERS_ENV = "KMC_HIP_CHECK_PART_MB"
+_KMER_SYMBOLS = frozenset(b"ACGTacgt")
+
+
+def parse_check(argv):
+    """-> ((path, ci, cx), kmer) (parameters_parser.cpp:704-708,228-236)"""
+    if not argv:
+        raise UsageError(CHECK_USAGE)
+    path, ci, cx, pos = _input_desc(argv, 0)
+    if pos >= len(argv):
+        raise UsageError("check operation require k-mer to check")
+    return (path, ci, cx), argv[pos]
+
+
+def _check_counters(db, ci, cx, kmers, ctx) -> np.ndarray:
+    """-> per k-mer the counter the database holds for it as given (0: none), after the rule of check_kmer.h:48,79: present while (uint32)(counter - ci) <
+    (uint32)(cx - ci) — a counter EQUAL to cx is absent, unlike in every other mode"""
+    k = db.kmer_len
+    lines = []
+    for kmer in kmers:
+        b = kmer.encode("latin-1") if isinstance(kmer, str) else bytes(kmer)
+        if len(b) != k:  # check_kmer.h:196-200
+            raise RefError("Error: invalid k-mer length")
+        lines.append(b)
+    for b in lines:
+        if not _KMER_SYMBOLS.issuperset(b):  # check_kmer.h:216-233
+            raise RefError("Error: invalid k-mer format")
+    out = np.zeros(len(lines), dtype=np.uint32)
+    if not lines:
+        return out
+    part = max(1, int(float(os.environ.get(CHECK_PART_KMERS_ENV, "64")) * (1 << 20)) // (k + 1))  # k-mers of a part: a line is k + 1 bytes
+    own = ctx is None
+    if own:
+        ctx = capi.Context((0,))
+    dev = None
+    try:
+        dev = _DeviceDb(ctx, db, order=True)  # one upload of the database
+        view = dev.view(0, U32_MAX)  # every record present: the rule is applied below
+        for first in range(0, len(lines), part):
+            seq = np.frombuffer(b"".join(ln + b"\n" for ln in lines[first:first + part]), dtype=np.uint8)
+            d_seq, d_cnt = ctx.malloc(seq.size + 256), ctx.malloc(4 * seq.size + 256)
+            try:
+                ctx.h2d(d_seq, seq)
+                ctx.db_query_reads_device(view, k, False, d_seq, seq.size, 0, 0, 0, d_cnt)
+                cnt = np.zeros(seq.size, dtype=np.uint32)
+                ctx.d2h(cnt, d_cnt)
+            finally:
+                ctx.free(d_seq)
+                ctx.free(d_cnt)
+            out[first:first + part] = cnt[::k + 1]  # the window that starts a line is the line's k-mer
+    finally:
+        if dev:
+            dev.free()
+        if own:
+            ctx.close()
+    present = ((out.astype(np.int64) - ci) & U32_MAX) < ((cx - ci) & U32_MAX)
+    return np.where(present, out, 0).astype(np.uint32)
+
+
+def check_kmers(db_path, kmers, ci=None, cx=None, ctx=None) -> np.ndarray:
+    """The batch form of `check`: the counters of `kmers` (text of k symbols each) in the database at db_path, uint32, 0 where `check` prints 0 or nothing. The
+    database goes up once; the k-mers go through in parts as lines of a reads buffer of kmc_hip_db_query_reads_device."""
+    (db, ci, cx), = _validated_inputs([(db_path, ci, cx)])
+    return _check_counters(db, ci, cx, list(kmers), ctx)
+
+
+def check(argv, ctx=None) -> str:
+    """Runs the command line; returns what kmc_tools prints: the counter and a line end — for a KFF file that does not hold the k-mer, nothing (check_kmer.h:375-401)"""
+    desc, kmer = parse_check(argv)
+    (db, ci, cx), = _validated_inputs([desc])
+    c = int(_check_counters(db, ci, cx, [kmer], ctx)[0])
+    return "" if isinstance(db, dbio.KffFile) and c == 0 else f"{c}\n"
+
+
+def info(argv) -> tuple:
+    """Runs the command line; returns (stdout text, stderr text) of CTools::info() (kmc_tools.cpp:139-224). Headers only: no device."""
+    if not argv:
+        raise UsageError(INFO_USAGE)
+    path, _, _, _ = _input_desc(argv, 0)
+    try:
+        if dbio.is_kff(path) and not os.path.exists(path + ".kmc_pre"):
+            return _info_kff(dbio.read_kff(path))
+        h = _read_header(path)
+        size = os.path.getsize(path + ".kmc_pre")
+        with open(path + ".kmc_pre", "rb") as f:
+            f.seek(size - 8)
+            header_offset = int.from_bytes(f.read(4), "little")
+    except (dbio.DbFormatError, OSError) as e:
+        raise UsageError(str(e))
+    if h.mode == 1:
+        raise UsageError("quality counters are not supported in kmc tools")
+    n_bins = 0
+    if h.kmc2:  # kmer_file_header.cpp:96-101, in its 32-bit arithmetic
+        single_lut, map_size = ((1 << (2 * h.lut_prefix_len)) * 8) & U32_MAX, (((1 << (2 * h.signature_len)) + 1) * 4) & U32_MAX
+        n_bins = ((size - 8 - 12 - header_offset - map_size) // single_lut) & U32_MAX
+    rows = [("k", h.kmer_len), ("total k-mers", h.total_kmers), ("cutoff max", h.max_count), ("cutoff min", h.min_count), ("counter size", f"{h.counter_size} bytes"),
+            ("mode", "quality-aware counters" if h.mode else "occurrence counters"), ("both strands", "yes" if h.both_strands else "no"),
+            ("database format", "KMC2.x" if h.kmc2 else "KMC1.x"), ("signature length", h.signature_len), ("number of bins", n_bins), ("lut_prefix_len", h.lut_prefix_len)]
+    return "".join("%-18s:  %s\n" % r for r in rows), ""
+
+
+def _info_kff(kff) -> tuple:
+    """kmc_tools.cpp:157-216. A raw section has no minimizer bytes: its `minimizer (HEX)` line is empty (and std::hex, set inside the loop over them, never is)"""
+    yes = lambda v: "yes" if v else "no"  # noqa: E731
+    out = ["This is KFF file, summary:\n", f"canonical         :  {yes(kff.both_strands)}\n", f"all k-mers unique :  {yes(kff.all_unique)}\n", "symbols encoding:\n"]
+    out += [f"\t{s}: {(kff.encoding >> sh) & 3}\n" for s, sh in zip("ACGT", (6, 4, 2, 0))]
+    err = []
+    for variables, sections in kff.scopes:
+        out += [f"k             :  {variables['k']}\n", f"data_size     :  {variables['data_size']}\n", f"max           :  {variables['max']}\n"]
+        if "m" in variables:
+            out.append(f"m             :  {variables['m']}\n")
+        err.append("footer values:\n")
+        err += [f"\t{name}      :  {value}\n" for name, value in sorted(kff.footer.items())]
+        out.append("Data sections:\n")
+        for start, n in sections:
+            out += ["\ttype            :  raw\n", f"\tdata_start      :  {start}\n", f"\tnb_blocks       :  {n}\n", "\tminimizer (HEX) :  \n"]
+        out.append(f"tot_nb_blocks :  {sum(n for _, n in sections)}\n")
+    return "".join(out), "".join(err)
+
+
 COUNT_USAGE = """usage: python -m kmc_amd.tools count [options] <input_file | @file_of_inputs> <out> [<working_dir>]
   the argument order of `kmc`, so a kmc command line carries over. Read: -k<len> (25; 14..224) -ci<v> (2) -cx<v> (1e9) -cs<v> (255) -b -fa | -fq (default) | -fm -hc
   -p<signature_len> (min(9, k); 5..11) -n<bins> (512; at most 2048). Accepted and ignored (they size the reference's host pipeline): -t* -m* -r -sf* -sp* -sr* -v and
@@ -1205,9 +1445,21 @@ def main(argv=None) -> int:
         st = complex(argv[1:])
         print(f"complex -> {parse_complex(open(argv[1]).read())['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
         return 0
+    if argv and argv[0] == "compare":
+        res = compare(argv[1:])
+        sys.stdout.write(compare_report(res))
+        return 0 if res["kind"] == "equal" else 1  # kmc_tools.cpp:518-527: exit(0), exit(1)
+    if argv and argv[0] == "check":
+        sys.stdout.write(check(argv[1:]))
+        return 0
+    if argv and argv[0] == "info":
+        out, err = info(argv[1:])
+        sys.stdout.write(out)
+        sys.stderr.write(err)
+        return 0
     if not argv or argv[0] != "simple":
         raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...\n" + FILTER_USAGE + "\n" + TRANSFORM_USAGE + "\n"
-                         + COMPLEX_USAGE + "\n" + COUNT_USAGE)
+                         + COMPLEX_USAGE + "\n" + COMPARE_USAGE + "\n" + CHECK_USAGE + "\n" + INFO_USAGE + "\n" + COUNT_USAGE)
     for (o, st) in zip(parse_simple(argv[1:])[1], simple(argv[1:])):
         print(f"{o['op']} -> {o['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
     return 0
