@@ -376,6 +376,30 @@ int kmc_hip_kff_import_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint
                               const uint64_t *section_n_recs /* host, [n_sections] */, uint32_t n_sections, uint32_t ordered, uint32_t out_lut_prefix_len, uint8_t *d_out,
                               uint64_t out_capacity, uint64_t *d_lut_out, uint64_t *n_kmers);
 
+/* ---- a database body framed as the records of a KFF file ------------------------------------------------
+ * The inverse of kmc_hip_kff_import_device, for KFF output: records [first, first + count) of the body db — packed records of (kmer_len - lut_prefix_len) / 4 suffix
+ * bytes and counter_size counter bytes, least significant first, under a LUT of record offsets — become count KFF records of ceil(kmer_len / 4) + data_size bytes in
+ * d_kff: the k-mer most significant byte first and right-aligned (the prefix bytes come back from the LUT: the prefix of record j is the index of the last LUT entry
+ * <= j), then data_size - counter_size zero bytes and the counter bytes most significant first. A large body goes through in parts, as the dump does.
+ *   n_lut_segments as for kmc_hip_db_dump_device: 1, an ordered body under a LUT of 4^lut_prefix_len entries; above 1, a KMC2 body (or an unordered KFF import) in file
+ *     order under n_lut_segments x 4^lut_prefix_len global record offsets and the closing entry; the prefix is the entry's index modulo 4^lut_prefix_len.
+ *   data_size: counter_size..4. The two writers of the reference size a set_counts output differently (kff_db_writer.h:74 takes MIN(BYTE_LOG(counter_max),
+ *     BYTE_LOG(cutoff_max)), kmc1_db_writer.h BYTE_LOG(counter_value)): a body made for the one can be framed for the other.
+ * db->cutoff_min and db->cutoff_max are NOT read: the body is an output — the entry that made it (kmc_hip_db_reduce_device, kmc_hip_db_set_op_device,
+ * kmc_hip_count_order ...) has already applied the writer's rule (kff_db_writer.h:101-109), and every record of the range is framed.
+ * Synchronous. count = 0 and an empty body are legal (d_recs and d_kff may then be NULL). No byte of d_kff outside [0, count x (ceil(kmer_len / 4) + data_size)) is
+ * touched. KMC_HIP_EINVAL: a NULL argument, counter_size outside 1..4, data_size outside counter_size..4, a lut_prefix_len the other kmc_hip_db_* entries refuse,
+ * kmer_len 0 or > 224, first + count > n_recs, n_lut_segments 0 or a LUT of 2^31 entries or more; KMC_HIP_ECAPACITY: kff_capacity (bytes) below what the range needs;
+ * KMC_HIP_ECORRUPT: a LUT that ends behind the records. Nothing is allocated.
+ * k_kff_frame works flat over tiles of 256 x ipt records, both images of a tile in LDS and moved as whole aligned 16-byte pieces; the tile's slice of the LUT is found
+ * by loads that are the same in every lane (a bisection for its first record, doubling steps to its last one); a thread bisects that slice for its first record, walks a
+ * few entries for each following one and bisects again where the next prefix lies further away, so a record costs O(log LUT entries) however sparse the LUT is. $KMC_HIP_KFF_IPT: records per thread, as for the import (default: 32 KiB of LDS per workgroup, at most 8, and lowered
+ * while that many records of either kind are a multiple of 64 bytes: neighbouring lanes would meet on one LDS bank).
+ * Replaces: CKFFDbWriter<SIZE>::add_kmer (kmc_tools/kff_db_writer.h:98-118), one k-mer at a time on one thread; the container around the records (CKFFWriter,
+ * kmc_core/kff_writer.cpp) stays on the host. */
+int kmc_hip_db_kff_export_device(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, const kmc_hip_db_view *db, uint32_t n_lut_segments, uint64_t first, uint64_t count,
+                                 uint32_t data_size, uint8_t *d_kff, uint64_t kff_capacity);
+
 /* ---- two ordered databases compared --------------------------------------------------------------------
  * `kmc_tools compare <db1> <db2>` on the device: a and b are ordered bodies as every kmc_hip_db_* entry takes them, of one kmer_len (<= 224); lut_prefix_len,
  * counter_size and cutoffs may differ. Semantics, the reference's: a record whose counter lies outside its view's [cutoff_min, cutoff_max] is absent

@@ -147,7 +147,7 @@ SYMBOLS = [
     "kmc_hip_sigstats_open", "kmc_hip_sigstats_part", "kmc_hip_sigstats_read", "kmc_hip_sigstats_close", "kmc_hip_sigstats_allowed",
     "kmc_hip_db_set_op_device", "kmc_hip_db_query_reads_device",
     "kmc_hip_db_reduce_device", "kmc_hip_db_histogram_device", "kmc_hip_db_dump_device",
-    "kmc_hip_db_expr_device", "kmc_hip_kff_import_device", "kmc_hip_db_compare_device",
+    "kmc_hip_db_expr_device", "kmc_hip_kff_import_device", "kmc_hip_db_compare_device", "kmc_hip_db_kff_export_device",
     "kmc_hip_count_open", "kmc_hip_count_part", "kmc_hip_count_finish", "kmc_hip_count_order", "kmc_hip_count_info", "kmc_hip_count_timings", "kmc_hip_count_close", "kmc_hip_debug_gather_segments",
 ]
 
@@ -253,6 +253,8 @@ def load():
         L.kmc_hip_db_compare_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.POINTER(DbView), u64p]
     if hasattr(L, "kmc_hip_kff_import_device"):  # added within ABI version 4
         L.kmc_hip_kff_import_device.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp, u64p, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp, u64p]
+    if hasattr(L, "kmc_hip_db_kff_export_device"):  # added within ABI version 4
+        L.kmc_hip_db_kff_export_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, vp, C.c_uint64]
     bind_count(L)
     _LIB = L
     return L
@@ -594,6 +596,13 @@ class Context:
         self._chk(self.L.kmc_hip_kff_import_device(self.h, dev, kmer_len, data_size, d_kff or None, sec, len(section_n_recs), 1 if ordered else 0, out_lut_prefix_len, d_out or None,
                                                    out_capacity, d_lut_out or None, C.byref(n)))
         return n.value
+
+    def db_kff_export_device(self, kmer_len: int, db: DbView, n_lut_segments: int, first: int, count: int, data_size: int, d_kff: int, kff_capacity: int, dev: int = 0) -> int:
+        """Records [first, first + count) of a device-resident body framed as KFF records of ceil(kmer_len / 4) + data_size bytes in d_kff (kmc_hip_db_kff_export_device);
+        n_lut_segments as for db_dump_device. The view's cutoffs are not read. Returns the bytes written."""
+        self._need("kmc_hip_db_kff_export_device")
+        self._chk(self.L.kmc_hip_db_kff_export_device(self.h, dev, kmer_len, C.byref(db), n_lut_segments, first, count, data_size, d_kff or None, kff_capacity))
+        return count * ((kmer_len + 3) // 4 + data_size)
 
     def debug_gather_segments(self, d_src: int, d_dst: int, table: np.ndarray, dev: int = 0):
         """test hook: k_cnt_gather on a table of (source offset, destination offset, bytes) triples over two device buffers"""

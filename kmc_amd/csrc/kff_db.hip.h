@@ -14,6 +14,8 @@
  *                 Workgroups behind the tiles write the entries of the empty sections. No 64-bit words, no width template.
  *   k_kff_unpack  one thread per record: (SIZE k-mer words, count word), the layout k_db_unpack leaves, for the sort of several sections into one body
  *   k_kff_verify  over the sorted records: neighbours strictly ascending (a k-mer present in two sections is corrupt: the reference would emit it twice)
+ *   k_kff_frame   the inverse of k_kff_repack, for KFF output (kmc_tools/kff_db_writer.h:98-118): the prefix bytes back from the LUT, the suffix bytes copied, the counter
+ *                 reversed and widened to the file's data_size; the same two images in LDS
  * k_kff_repack and k_kff_unpack verify what they read: the padding bits are zero and the prefix is below 4^p (with (k - p) % 4 == 0 the padding bits are the top bits of
  * the prefix bytes: one comparison), and every record is strictly greater than its predecessor in its section, compared on the big-endian bytes. A violation lowers
  * *bad to the smallest offending record number; nothing outside the outputs is written (a prefix out of range writes no LUT entry).
@@ -188,6 +190,98 @@ __global__ void __launch_bounds__(KFF_THREADS) k_kff_repack(const uint8_t *__res
 	}
 	if (worst != KFF_NONE)
 		atomicMin(bad, worst);
+	__syncthreads();
+	kff_copy_aligned(dst, img_out, mis_out, len * rb_out, tid);
+}
+
+/* ---- the inverse: a database body framed as KFF records (CKFFDbWriter<SIZE>::add_kmer, kmc_tools/kff_db_writer.h:98-118) ---- */
+constexpr u32 KFF_WALK = 4; /* LUT entries a thread walks from one record's prefix towards the next one's before it bisects what is left */
+struct KffFrame {
+	u32 p, kbytes /* ceil(k / 4) */, sbytes /* (k - p) / 4 */, cbytes /* the body's counter bytes */, dbytes /* the file's data_size >= cbytes */;
+	u32 n_entries; /* of the LUT: segments x 4^p (the closing entry of a segmented LUT is not counted) */
+	u32 ipt;
+};
+/* the image of the records read, up to 15 bytes of alignment slack, a multiple of 16; behind it the image of the records written and its slack */
+constexpr size_t kff_frame_in_lds_bytes(u32 tile, u32 rb_in) { return (((size_t)tile * rb_in + 16) + 15) & ~(size_t)15; }
+constexpr size_t kff_frame_lds_bytes(u32 tile, u32 rb_in, u32 rb_out) { return kff_frame_in_lds_bytes(tile, rb_in) + (size_t)tile * rb_out + 16; }
+
+/* the last entry of lut[lo .. hi) that is <= j, where lut[lo] <= j */
+__device__ __forceinline__ u32 kff_last_entry(const u64 *__restrict__ lut, u32 lo, u32 hi, u64 j)
+{
+	while (hi - lo > 1) {
+		const u32 mid = lo + ((hi - lo) >> 1);
+		if (lut[mid] <= j)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+/* the same by doubling steps from lo and a bisection of the last step: O(log distance) loads — one or two where the answer lies next to lo */
+__device__ __forceinline__ u32 kff_last_entry_near(const u64 *__restrict__ lut, u32 lo, u32 hi, u64 j)
+{
+	u32 step = 1;
+	while (hi - lo > step && lut[lo + step] <= j) {
+		lo += step;
+		step <<= 1;
+	}
+	return kff_last_entry(lut, lo, hi - lo > step ? lo + step : hi, j);
+}
+
+/* Workgroup t: records [first + t x tile, first + (t + 1) x tile) of the body (sbytes suffix bytes, cbytes counter bytes least significant first) -> records t x tile ..
+ * of out: pbytes = kbytes - sbytes prefix bytes most significant first, the suffix bytes verbatim, dbytes - cbytes zero bytes, the counter bytes reversed. The prefix of
+ * record j is the index of the last LUT entry <= j, modulo 4^p under a segmented LUT (kmc2_db_reader.h:1776-1791); with (k - p) % 4 == 0 its value below 4^p leaves the
+ * padding bits of the first byte zero. The search has two levels. Every thread bisects the whole LUT for the TILE's first record and steps on from there to the tile's
+ * last one: the addresses are the same in all lanes (block index and kernel arguments only), so these are scalar loads, and the upper levels of the bisection are the
+ * same words for every tile. A thread then takes ipt consecutive records: it bisects the tile's slice of the LUT for the first one — a word or two where the LUT is
+ * dense —; for each following one it walks at most KFF_WALK entries and bisects the rest of the slice where that was not enough. So a record costs O(log entries) loads
+ * whether the LUT is dense or five records lie under 4^9 entries (the walk gives up, the bisection is over what is left). Both images lie in LDS at the byte offset they
+ * have inside their 16 bytes of HBM and move as whole aligned pieces (kff_copy_aligned). Nothing outside out[0 .. count x (kbytes + dbytes)) is written. No wave-wide
+ * step: a thread without records does nothing between the two barriers. */
+__global__ void __launch_bounds__(KFF_THREADS) k_kff_frame(const uint8_t *__restrict__ recs, const u64 *__restrict__ lut, u64 first, u64 count, KffFrame g, uint8_t *__restrict__ out)
+{
+	KMC_DYN_LDS(uint8_t, s_img);
+	const u32 tid = threadIdx.x, tile = KFF_THREADS * g.ipt, rb_in = g.sbytes + g.cbytes, rb_out = g.kbytes + g.dbytes, pbytes = g.kbytes - g.sbytes, pad = g.dbytes - g.cbytes;
+	const u64 l0 = (u64)blockIdx.x * tile;
+	const u32 len = (u32)(count - l0 < (u64)tile ? count - l0 : (u64)tile);
+	/* the tile's slice of the LUT: entries [t_lo, t_end), t_lo the entry of its first record, t_end - 1 the entry of its last one (len >= 1: the grid has no empty tile) */
+	const u32 t_lo = kff_last_entry(lut, 0u, g.n_entries, first + l0);
+	const u32 t_end = kff_last_entry_near(lut, t_lo, g.n_entries, first + l0 + len - 1) + 1;
+	const uint8_t *src = recs + (first + l0) * rb_in;
+	uint8_t *dst = out + l0 * rb_out;
+	const u32 mis_in = (u32)((size_t)src & 15), mis_out = (u32)((size_t)dst & 15);
+	uint8_t *img_in = s_img + mis_in, *img_out = s_img + kff_frame_in_lds_bytes(tile, rb_in) + mis_out;
+	kff_copy_aligned(img_in, src, mis_in, len * rb_in, tid);
+	__syncthreads();
+	const u32 m0 = tid * g.ipt < len ? tid * g.ipt : len, m1 = m0 + g.ipt < len ? m0 + g.ipt : len;
+	if (m0 < m1) {
+		const u32 pmask = (1u << (2 * g.p)) - 1;
+		u32 lo = kff_last_entry(lut, t_lo, t_end, first + l0 + m0);
+		for (u32 m = m0; m < m1; ++m) {
+			const u64 j = first + l0 + m;
+			u32 w = 0;
+#pragma unroll 1
+			while (w < KFF_WALK && lo + 1 < t_end && lut[lo + 1] <= j)
+				++lo, ++w;
+			if (w == KFF_WALK)
+				lo = kff_last_entry(lut, lo, t_end, j);
+			const uint8_t *r = img_in + (size_t)m * rb_in;
+			uint8_t *o = img_out + (size_t)m * rb_out;
+			const u32 x = lo & pmask;
+#pragma unroll 1
+			for (u32 q = 0; q < pbytes; ++q)
+				o[q] = (uint8_t)(x >> (8 * (pbytes - 1 - q)));
+#pragma unroll 1
+			for (u32 q = 0; q < g.sbytes; ++q)
+				o[pbytes + q] = r[q];
+#pragma unroll 1
+			for (u32 q = 0; q < pad; ++q)
+				o[g.kbytes + q] = 0;
+#pragma unroll 1
+			for (u32 q = 0; q < g.cbytes; ++q)
+				o[g.kbytes + pad + q] = r[g.sbytes + g.cbytes - 1 - q];
+		}
+	}
 	__syncthreads();
 	kff_copy_aligned(dst, img_out, mis_out, len * rb_out, tid);
 }

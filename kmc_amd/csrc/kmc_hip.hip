@@ -620,3 +620,4 @@ struct DevTemps {
 #include "host_expr.hip.h" /* a set expression over several ordered databases (`kmc_tools complex`) */
 #include "host_compare.hip.h" /* two ordered databases compared (`kmc_tools compare`) */
 #include "host_kff.hip.h" /* the records of a KFF file imported as a database body (the KFF inputs of every `kmc_tools` database mode) */
+#include "host_kff_export.hip.h" /* a database body framed as the records of a KFF file (KFF output) */

@@ -1,6 +1,6 @@
 """KMC databases on disk <-> numpy: what `python -m kmc_amd.tools` reads and writes.
 
-read_kff() takes a KFF file (kmc_core/kff_writer.cpp) as kmc_tools' CKFFInfoReader does.
+read_kff() takes a KFF file (kmc_core/kff_writer.cpp) as kmc_tools' CKFFInfoReader does; write_kff() writes one as CKFFWriter does.
 read_database() takes a database as `kmc` writes it (KMC2: records ordered inside every signature bin, kmc_core/kb_completer.cpp:287-320) or as `kmc_tools`
 writes it (KMC1: one ascending sequence, kmc_tools/kmc1_db_writer.h:296-372); the header is parsed as kmc_tools/kmer_file_header.cpp:63-93 does.
 write_kmc1() writes the KMC1 form: markers, LUT, header, records."""
@@ -224,6 +224,47 @@ def read_kff(path: str) -> KffFile:
             raise bad(f"truncated (the raw section at byte {off - 9} announces {n} records of {rb} bytes)")
     return KffFile(name, k, sizes[0], footer.get("min_count", 1), footer.get("max_count", 0xFFFFFFFF), bool(canonical), sections, b,
                    scopes=[(dict(v), list(secs)) for v, secs in scopes], encoding=encoding, all_unique=all_unique, footer=dict(footer))
+
+
+def write_kff(path: str, kmer_len: int, data_size: int, both_strands: bool, min_count: int, max_count: int, sections) -> None:
+    """The file CKFFWriter writes (kmc_core/kff_writer.cpp): 'KFF' 1 0 encoding all_unique = 1 canonical, an empty free block, the 'v' section (k, max = 1, data_size,
+    ordered = 1), one 'r' section per element of `sections`, the index (offsets relative to its own end; its last entry the footer, next_index 0), the footer
+    (first_index, min_count, max_count, counter_size, footer_size) and 'KFF'. An element of `sections` is the section's record bytes (bytes or a uint8 array), or an
+    iterable of such pieces — the parts of a large export, written as they come; the section's record count is derived from the bytes and, as by InitSection /
+    FinishSection (:92-127), written into its place afterwards. An output without records is ONE section of no records: the caller passes [b""]."""
+    rb = (kmer_len + 3) // 4 + data_size
+    be8 = lambda v: (int(v) & ((1 << 64) - 1)).to_bytes(8, "big")  # noqa: E731
+
+    def variables(pairs):
+        return b"v" + be8(len(pairs)) + b"".join(name.encode() + b"\0" + be8(val) for name, val in pairs)
+
+    with open(path, "wb") as f:
+        f.write(b"KFF" + bytes([1, 0, KFF_ENCODING, 1, 1 if both_strands else 0]) + (0).to_bytes(4, "big"))
+        index = [f.tell()]
+        f.write(variables([("k", kmer_len), ("max", 1), ("data_size", data_size), ("ordered", 1)]))
+        for sec in sections:
+            index.append(f.tell())
+            f.write(b"r" + be8(0))
+            n_bytes = 0
+            for piece in ([sec] if isinstance(sec, (bytes, bytearray, memoryview, np.ndarray)) else sec):
+                data = piece.tobytes() if isinstance(piece, np.ndarray) else bytes(piece)
+                f.write(data)
+                n_bytes += len(data)
+            if n_bytes % rb:
+                raise ValueError(f"write_kff: a section of {n_bytes} bytes is no whole number of records of {rb} bytes")
+            if n_bytes:
+                f.seek(index[-1] + 1)
+                f.write(be8(n_bytes // rb))
+                f.seek(0, os.SEEK_END)
+        index_start = f.tell()
+        index_end = index_start + 1 + 8 + (len(index) + 1) * 9 + 8
+        f.write(b"i" + be8(len(index) + 1))
+        for i, pos in enumerate(index):
+            f.write((b"v" if i == 0 else b"r") + be8(pos - index_end))
+        f.write(b"v" + be8(0) + be8(0))
+        footer = [("first_index", index_start), ("min_count", min_count), ("max_count", max_count), ("counter_size", data_size)]
+        footer.append(("footer_size", 1 + 8 + sum(len(n) + 1 + 8 for n, _ in footer) + len("footer_size") + 1 + 8))
+        f.write(variables(footer) + b"KFF")
 
 
 def read_database(path: str) -> Database:

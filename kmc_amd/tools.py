@@ -5,6 +5,7 @@ python -m kmc_amd.tools complex <operations_definition_file>
 python -m kmc_amd.tools compare <db1> [-ci<v> -cx<v>] <db2> [-ci<v> -cx<v>]
 python -m kmc_amd.tools check <db> [-ci<v> -cx<v>] <kmer>
 python -m kmc_amd.tools info <db>
+python -m kmc_amd.tools export <db> [-ci<v> -cx<v>] <out> [-ci<v> -cx<v> -cs<v>] [--sections]
 
 `kmc_tools simple`, `kmc_tools filter`, `kmc_tools transform` and `kmc_tools complex` on the device: the argument order and the defaults are the reference's (kmc_tools/parameters_parser.cpp),
 the databases, the reads and the text written are byte for byte those kmc_tools writes. simple: one kmc_hip_db_set_op_device call per output. filter: one
@@ -171,6 +172,48 @@ class _DeviceDb:
         self.allocs = []
 
 
+OUTPUT_FORMATS = ("kmc1", "kff")
+
+
+def _kff_parts(ctx, k, body: capi.DbView, n_seg, first, count, data_size):
+    """records [first, first + count) of the body as KFF record bytes, part by part ($KMC_HIP_KFF_PART_MB of records a part, 64 by default): one
+    kmc_hip_db_kff_export_device call and one copy to the host per part — what write_kff takes as one section"""
+    rb = (k + 3) // 4 + data_size
+    part_bytes = max(1, int(float(os.environ.get("KMC_HIP_KFF_PART_MB", "64")) * (1 << 20)))
+    part = max(1, part_bytes // rb)
+    if not count:
+        return
+    cap = min(part, count) * rb
+    d_kff = ctx.malloc(cap + 256)
+    try:
+        for at in range(first, first + count, part):
+            n_bytes = ctx.db_kff_export_device(k, body, n_seg, at, min(part, first + count - at), data_size, d_kff, cap)
+            out = np.zeros(n_bytes, dtype=np.uint8)
+            ctx.d2h(out, d_kff)
+            yield out
+    finally:
+        ctx.free(d_kff)
+
+
+def _write_body(ctx, fmt: str, path: str, k: int, body: capi.DbView, ci: int, cx: int, both_strands: bool, mode: int = 0, n_seg: int = 1, sections=None):
+    """The one place an output body leaves the device. body: a view of the records an entry wrote (its cutoffs are not read). fmt "kmc1": records and LUT come down and
+    `path`.kmc_pre / .kmc_suf are written (n_seg 1). fmt "kff": the records are framed on the device and only KFF bytes come down; `path`.kff is written, as the
+    reference appends the extension (kff_db_writer.h:79), with one section — or, with `sections` = [(first record, records)], one per element."""
+    if fmt not in OUTPUT_FORMATS:
+        raise ValueError(f"an output body is written as one of {OUTPUT_FORMATS}, not {fmt!r}")
+    n, p, cs = int(body.n_recs), int(body.lut_prefix_len), int(body.counter_size)
+    if fmt == "kff":
+        secs = [(0, n)] if sections is None else sections
+        dbio.write_kff(path + ".kff", k, cs, both_strands, ci, cx, [_kff_parts(ctx, k, body, n_seg, first, count, cs) for first, count in secs])
+        return
+    assert n_seg == 1 and sections is None
+    recs, lut = np.zeros(n * ((k - p) // 4 + cs), dtype=np.uint8), np.zeros(1 << (2 * p), dtype=np.uint64)
+    if n:
+        ctx.d2h(recs, body.d_recs)
+    ctx.d2h(lut, body.d_lut)
+    dbio.write_kmc1(path, k, cs, p, ci, cx, both_strands, lut, recs, mode=mode)
+
+
 def simple(argv, ctx=None) -> list:
     """Runs the command line; returns per output the dict of tallies of kmc_hip_db_set_op_device."""
     inputs, outputs = parse_simple(argv)
@@ -211,14 +254,10 @@ def simple(argv, ctx=None) -> list:
             d_out, d_lut = ctx.malloc(bound * rb + 256), ctx.malloc(8 << (2 * p_out))
             try:
                 n, st = ctx.db_set_op_device(k, views[0], views[1], op, d_out, bound * rb, d_lut)
-                recs, lut = np.zeros(n * rb, dtype=np.uint8), np.zeros(1 << (2 * p_out), dtype=np.uint64)
-                if n:
-                    ctx.d2h(recs, d_out)
-                ctx.d2h(lut, d_lut)
+                _write_body(ctx, "kmc1", o["path"], k, capi.DbView(d_out, n, d_lut, p_out, cs_bytes, ci, cx), ci, cx, canonical, mode=dbs[0].mode)
             finally:
                 ctx.free(d_out)
                 ctx.free(d_lut)
-            dbio.write_kmc1(o["path"], k, cs_bytes, p_out, ci, cx, canonical, lut, recs, mode=dbs[0].mode)
             results.append(st)
     finally:
         for d in dev:
@@ -539,21 +578,17 @@ def resolve_transform(outputs, db: dbio.Database, in_ci: int, in_cx: int) -> lis
     return res
 
 
-def _transform_database(ctx, dev, view, db, r) -> dict:
+def _transform_database(ctx, dev, view, db, r, fmt="kmc1") -> dict:
     k = db.kmer_len
-    p_out = dbio.best_lut_prefix_len(k, db.total_kmers)  # kmc1_db_writer.h:425-456, over the input header's total
+    p_out = dbio.best_lut_prefix_len(k, db.total_kmers)  # kmc1_db_writer.h:425-456, over the input header's total; a KFF output does not show it
     rb = (k - p_out) // 4 + r["cs_bytes"]
     d_out, d_lut = ctx.malloc(dev.n * rb + 256), ctx.malloc(8 << (2 * p_out))
     try:
         n, st = ctx.db_reduce_device(k, view, r["ci"], r["cx"], min(r["cs"], U32_MAX), r["value"], p_out, d_out, dev.n * rb, d_lut)
-        recs, lut = np.zeros(n * rb, dtype=np.uint8), np.zeros(1 << (2 * p_out), dtype=np.uint64)
-        if n:
-            ctx.d2h(recs, d_out)
-        ctx.d2h(lut, d_lut)
+        _write_body(ctx, fmt, r["path"], k, capi.DbView(d_out, n, d_lut, p_out, r["cs_bytes"], r["ci"], r["cx"]), r["ci"], r["cx"], db.both_strands, mode=db.mode)
     finally:
         ctx.free(d_out)
         ctx.free(d_lut)
-    dbio.write_kmc1(r["path"], k, r["cs_bytes"], p_out, r["ci"], r["cx"], db.both_strands, lut, recs, mode=db.mode)
     return st
 
 
@@ -638,6 +673,79 @@ def transform(argv, ctx=None) -> list:
         if own:
             ctx.close()
     return results
+
+
+EXPORT_USAGE = """usage: python -m kmc_amd.tools export <db> [-ci<v> -cx<v>] <out> [-ci<v> -cx<v> -cs<v>] [--sections]
+  writes <out>.kff, byte for byte the file of `kmc_tools transform <db> [-ci -cx] reduce <out> [-ci -cx -cs] -okff`: <db> (a KMC database as kmc or kmc_tools wrote
+  it, or a KFF file of one or many sections) ordered where it is not, reduced by the bounds (defaults as for transform's reduce), framed as KFF records on the device
+  and written as ONE ordered section.
+  --sections  a KMC2 database (as `kmc` wrote it) only, and without any bounds: the body stays in file order and every bin that is not empty becomes one KFF section,
+              under the input's own header values; no sort and no reduce. kmc_tools always orders, so this form has no reference twin: the file reads back (as an
+              input of any mode here, or of kmc_tools) as the same k-mers and counters."""
+
+
+def parse_export(argv):
+    """-> ((path, ci, cx), dict(path, ci, cx, cs, sections)); ci / cx / cs None = not given"""
+    if not argv or argv[0].startswith("-"):
+        raise UsageError("export needs an input database\n" + EXPORT_USAGE)
+    (path, ci, cx), pos = (argv[0], None, None), 1
+    while pos < len(argv) and argv[pos].startswith("-") and argv[pos] != "--sections":
+        if argv[pos].startswith("-ci"):
+            ci = _num1(argv[pos], "-ci")
+        elif argv[pos].startswith("-cx"):
+            cx = _num1(argv[pos], "-cx")
+        else:
+            raise UsageError(f"unknown input option {argv[pos]}\n" + EXPORT_USAGE)
+        pos += 1
+    o = dict(path=None, ci=None, cx=None, cs=None, sections=False)
+    for a in argv[pos:]:
+        if a == "--sections":
+            o["sections"] = True
+        elif not a.startswith("-"):
+            if o["path"] is not None:
+                raise UsageError(f"export writes one output ({o['path']}, then {a})\n" + EXPORT_USAGE)
+            o["path"] = a
+        elif o["path"] is not None and a[:3] in ("-ci", "-cx", "-cs"):
+            o[a[1:3]] = _num1(a, a[:3])
+        else:
+            raise UsageError(f"Unknown parameter: {a}\n" + EXPORT_USAGE)
+    if o["path"] is None:
+        raise UsageError("Output path missed (export)\n" + EXPORT_USAGE)
+    if o["sections"] and any(v is not None for v in (ci, cx, o["ci"], o["cx"], o["cs"])):
+        raise UsageError("export --sections copies the bins as they are: no -ci, -cx or -cs goes with it\n" + EXPORT_USAGE)
+    return (path, ci, cx), o
+
+
+def export(argv, ctx=None) -> dict:
+    """Runs the command line; returns the dict of tallies of kmc_hip_db_reduce_device (--sections: n_written and n_sections)."""
+    (path, ci, cx), o = parse_export(argv)
+    try:
+        db = _read_input(path)
+    except (dbio.DbFormatError, OSError) as e:
+        raise UsageError(str(e))
+    if db.counter_size == 0:
+        raise UsageError(f"{path}: counter size 0 (a k-mer set without counters) is not supported, as in kmc_tools")
+    if o["sections"] and not db.kmc2:
+        raise UsageError(f"{path}: export --sections takes a KMC2 database (as `kmc` wrote it); this input is " + ("a KFF file" if isinstance(db, dbio.KffFile) else "ordered already") + "\n" + EXPORT_USAGE)
+    in_ci, in_cx = ci or db.min_count, cx or db.max_count
+    r, = resolve_transform([dict(op="reduce", path=o["path"], ci=o["ci"], cx=o["cx"], cs=o["cs"], value=0)], db, in_ci, in_cx)
+    own = ctx is None
+    if own:
+        ctx = capi.Context((0,))
+    dev = None
+    try:
+        dev = _DeviceDb(ctx, db, order=not o["sections"])
+        if not o["sections"]:
+            return _transform_database(ctx, dev, dev.view(max(in_ci, 0), in_cx), db, r, fmt="kff")
+        starts = db.raw_lut[:: 1 << (2 * db.lut_prefix_len)].astype(np.int64)  # the bins' first records, then the closing entry (n_bins x 4^p + 1 entries)
+        secs = [(int(a), int(b - a)) for a, b in zip(starts[:-1], starts[1:]) if b > a] or [(0, 0)]
+        _write_body(ctx, "kff", o["path"], db.kmer_len, dev.view(db.min_count, db.max_count), db.min_count, db.max_count, db.both_strands, n_seg=dev.n_seg, sections=secs)
+        return dict(n_written=dev.n, n_sections=len(secs))
+    finally:
+        if dev:
+            dev.free()
+        if own:
+            ctx.close()
 
 
 COMPLEX_USAGE = """usage: python -m kmc_amd.tools complex <operations_definition_file>
@@ -898,14 +1006,10 @@ def complex(argv, ctx=None) -> dict:  # noqa: A001 (the mode's name)
         d_out, d_lut = ctx.malloc(bound * rb + 256), ctx.malloc(8 << (2 * r["p_out"]))
         try:
             n, st = ctx.db_expr_device(k, views, steps, capi.DbOp(0, 0, r["ci"], r["cs"], r["cx"], r["p_out"]), d_out, bound * rb, d_lut)
-            recs, lut = np.zeros(n * rb, dtype=np.uint8), np.zeros(1 << (2 * r["p_out"]), dtype=np.uint64)
-            if n:
-                ctx.d2h(recs, d_out)
-            ctx.d2h(lut, d_lut)
+            _write_body(ctx, "kmc1", o["path"], k, capi.DbView(d_out, n, d_lut, r["p_out"], r["cs_bytes"], r["ci"], r["cx"]), r["ci"], r["cx"], r["canonical"], mode=dbs[0].mode)
         finally:
             ctx.free(d_out)
             ctx.free(d_lut)
-        dbio.write_kmc1(o["path"], k, r["cs_bytes"], r["p_out"], r["ci"], r["cx"], r["canonical"], lut, recs, mode=dbs[0].mode)
     finally:
         for d in dev.values():
             d.free()
@@ -1151,7 +1255,8 @@ def _info_kff(kff) -> tuple:
 COUNT_USAGE = """usage: python -m kmc_amd.tools count [options] <input_file | @file_of_inputs> <out> [<working_dir>]
   the argument order of `kmc`, so a kmc command line carries over. Read: -k<len> (25; 14..224) -ci<v> (2) -cx<v> (1e9) -cs<v> (255) -b -fa | -fq (default) | -fm -hc
   -p<signature_len> (min(9, k); 5..11) -n<bins> (512; at most 2048). Accepted and ignored (they size the reference's host pipeline): -t* -m* -r -sf* -sp* -sr* -v and
-  <working_dir>. Everything else is refused. Writes <out>.kmc_pre / .kmc_suf as `kmc` followed by `kmc_tools transform <db> sort <out>` does."""
+  <working_dir>. Everything else is refused. Writes <out>.kmc_pre / .kmc_suf as `kmc` followed by `kmc_tools transform <db> sort <out>` does; with
+  KMC_HIP_COUNT_OUT=kff in the environment <out>.kff instead, as `kmc -okff` followed by `kmc_tools transform <out>.kff reduce <out2> -okff` does."""
 COUNT_PART_BYTES = 32 << 20
 COUNT_MAP_MULTIPLIER = 0x9E3779B1
 _COUNT_REFUSED = {"-okff": "KFF output", "-e": "the k-mer number estimation alone", "--opt-out-size": "the output size optimisation", "-fbam": "BAM input (the session entry takes BAM parts; "
@@ -1345,15 +1450,19 @@ def multiline_parts(path: str, part_bytes: int):
         yield strip(rest)
 
 
-def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_MULTIPLIER, signature_map="fixed"):
+def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_MULTIPLIER, signature_map="fixed", output_format="kmc"):
     """`kmc` + `kmc_tools transform sort` on the device: the reads of the input files go through a counting session (capi.CountSession) part by part, the ordered body is
     written as a KMC1 database. Returns dict(stats = the four tallies of stage 2 by name, totals = reads, super-k-mers, k-mers, bytes of bin records, n_records, n_parts,
     n_segments, n_batches, balance = k-mers of the largest bin / of the mean bin, map = the signature map that ran); keep=True: (that dict, the open session, its view) —
     the caller goes on on the device and closes the session.
     signature_map: "fixed" = count_signature_map's spread; "stats" = stage 0 first: the first part of every input file through capi.SigStats, the map from
-    balanced_signature_map. With fewer than COUNT_MAP_MIN_BINS bins "stats" keeps the fixed map and the result says so. The database does not depend on the map."""
+    balanced_signature_map. With fewer than COUNT_MAP_MIN_BINS bins "stats" keeps the fixed map and the result says so. The database does not depend on the map.
+    output_format: "kmc" = <out>.kmc_pre / .kmc_suf; "kff" = <out>.kff as `kmc -okff` followed by `kmc_tools transform <out>.kff reduce <out2> -okff` writes it (one
+    ordered section, min_count = -ci, max_count = -cx, canonical = not -b): the session's view goes to kmc_hip_db_kff_export_device and only KFF bytes come down."""
     if signature_map not in ("fixed", "stats"):
         raise ValueError(f'count: signature_map is "fixed" or "stats", not {signature_map!r}')
+    if output_format not in ("kmc", "kff"):
+        raise ValueError(f'count: output_format is "kmc" or "kff", not {output_format!r}')
     o = parse_count(argv)
     if part_bytes is None:
         part_bytes = int(os.environ.get("KMC_HIP_COUNT_PART_MB", "0")) << 20 or COUNT_PART_BYTES
@@ -1394,12 +1503,8 @@ def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_
         info = ses.info()
         p_out = dbio.best_lut_prefix_len(k, n_records)
         view = ses.order(p_out)
-        rb = (k - p_out) // 4 + view.counter_size
-        recs, lut = np.zeros(n_records * rb, dtype=np.uint8), np.zeros(1 << (2 * p_out), dtype=np.uint64)
-        if n_records:
-            ctx.d2h(recs, view.d_recs)
-        ctx.d2h(lut, view.d_lut)
-        dbio.write_kmc1(o["out"], k, view.counter_size, p_out, o["ci"], o["cx"], o["both"], lut, recs)
+        assert view.n_recs == n_records
+        _write_body(ctx, "kff" if output_format == "kff" else "kmc1", o["out"], k, view, o["ci"], o["cx"], o["both"])
         res = dict(stats=dict(zip(("n_unique", "n_below_min", "n_above_max", "n_total"), (int(x) for x in st))),
                    totals=dict(zip(("n_reads", "n_superkmers", "n_kmers", "bin_bytes"), (int(x) for x in tot))), n_records=n_records, n_parts=n_parts,
                    n_segments=info["n_segments"], n_batches=info["n_batches"], balance=info["largest_bin"] * o["n_bins"] / max(int(tot[2]), 1), map=signature_map)
@@ -1428,7 +1533,12 @@ def count_report(res: dict) -> str:
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if argv and argv[0] == "count":
-        print(count_report(count(argv[1:], signature_map="stats" if os.environ.get("KMC_HIP_COUNT_MAP") == "stats" else "fixed")))
+        print(count_report(count(argv[1:], signature_map="stats" if os.environ.get("KMC_HIP_COUNT_MAP") == "stats" else "fixed",
+                                 output_format="kff" if os.environ.get("KMC_HIP_COUNT_OUT") == "kff" else "kmc")))
+        return 0
+    if argv and argv[0] == "export":
+        out = parse_export(argv[1:])[1]["path"]
+        print(f"export -> {out}.kff: " + ", ".join(f"{a} {b}" for a, b in export(argv[1:]).items()))
         return 0
     if argv and argv[0] == "filter":
         print(", ".join(f"{a} {b}" for a, b in filter_reads(argv[1:]).items()))
@@ -1459,7 +1569,7 @@ def main(argv=None) -> int:
         return 0
     if not argv or argv[0] != "simple":
         raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...\n" + FILTER_USAGE + "\n" + TRANSFORM_USAGE + "\n"
-                         + COMPLEX_USAGE + "\n" + COMPARE_USAGE + "\n" + CHECK_USAGE + "\n" + INFO_USAGE + "\n" + COUNT_USAGE)
+                         + COMPLEX_USAGE + "\n" + COMPARE_USAGE + "\n" + CHECK_USAGE + "\n" + INFO_USAGE + "\n" + COUNT_USAGE + "\n" + EXPORT_USAGE)
     for (o, st) in zip(parse_simple(argv[1:])[1], simple(argv[1:])):
         print(f"{o['op']} -> {o['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
     return 0
