@@ -605,7 +605,8 @@ int kmc_hip_estimate_close(kmc_hip_ctx *ctx, int dev);
  * CKMC::AdjustMemoryLimitsSmallK kmc.h:677-750): every CWSmallKSplitter worker (splitter.h:138, splitter.cpp:929-983) keeps one table of 4^k counters that
  * CSplitter::ProcessReadsSmallK (splitter.cpp:682-805) increments once per k-mer, and stage 2 (ProcessSmallKOptimization_Stage2 kmc.h:865-960, CSmallKCompleter)
  * sums the workers' tables and writes the database. These entries keep ONE such table on `dev` (k_s1_smallk_count); the caller hands it to the reference's
- * stage 2 as one worker's table. Ask kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_SMALLK) first.
+ * stage 2 as one worker's table (kmc_hip_smallk_read), or turns it into the database where it lies (kmc_hip_smallk_tally / kmc_hip_smallk_view_device below). Ask
+ * kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_SMALLK) first.
  * _open : replaces the reserve + memset of CWSmallKSplitter::operator() (splitter.cpp:954-955): allocates and zeroes 4^kmer_len uint64 counters (8 bytes at
  *         k = 1, 512 MB at k = 13); kmer_len 1..13. Opening again with the same (kmer_len, both_strands) is a no-op, with another pair KMC_HIP_EINVAL.
  * _part : replaces CSplitter::ProcessReadsSmallK for one part (splitter.cpp:682-805, with GetSeq :88-421 and HomopolymerCompressSeq :424-435 in front): every
@@ -624,6 +625,32 @@ int kmc_hip_smallk_open(kmc_hip_ctx *ctx, int dev, uint32_t kmer_len, uint32_t b
 int kmc_hip_smallk_part(kmc_hip_ctx *ctx, int dev, int slot, const kmc_hip_split_params *p, const uint8_t *text, uint64_t size, uint64_t *n_reads, uint64_t *n_kmers);
 int kmc_hip_smallk_read(kmc_hip_ctx *ctx, int dev, uint64_t first, uint64_t count, uint64_t *dst);
 int kmc_hip_smallk_close(kmc_hip_ctx *ctx, int dev);
+
+/* ---- small k, stage 2 on the device: the table as a database (added within ABI version 4, like the entries above) ----
+ * Replaces CSmallKCompleter::CompleteKMCFormat / CompleteKFFFormat (kb_completer.h:149-378) for a caller that goes on on the device or writes the files itself: the
+ * table of 4^kmer_len uint64 counters — d_table, or with d_table == NULL the one kmc_hip_smallk_open made on `dev`; then kmer_len must be the open table's, and the
+ * kmc_hip_smallk_part calls in flight on `dev` are waited for, as _read does — is its own database order (the index is the k-mer), so k_sk_tally / k_db_cumsum /
+ * k_sk_emit compact and frame it without a sort. The table is not modified (the reference clamps in place). An entry c != 0 is unique; c < cutoff_min is below,
+ * c > cutoff_max above, everything else kept, in 64-bit arithmetic (counts above 2^32 are ordinary: poly-A, k = 1). Both entries are synchronous.
+ * Ask kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_SMALLK_DB) first.
+ * _tally      : stats[4] = unique, below, above, kept — what kmc prints, what a caller sizes d_out by and chooses out_lut_prefix_len from (kmc.h:906-936).
+ * _view_device: the kept entries in index order as records in d_out, *n_kmers of them, and the same stats[4]. counter_size = kmc_hip_counter_size(cutoff_max,
+ *               counter_max). framing 0, KMC1: (kmer_len - out_lut_prefix_len) / 4 suffix bytes, most significant first (0..3; none is what k <= 4 gets), then
+ *               counter_size bytes of min(count, counter_max), least significant first; d_lut_out receives all 4^out_lut_prefix_len entries (the kept entries in front
+ *               of the prefix's first k-mer); *view is filled as kmc_hip_count_order fills it, and for kmer_len - out_lut_prefix_len >= 4 every kmc_hip_db_* entry takes
+ *               it. A body without suffix bytes is for files only: the other entries refuse it. framing 1, KFF: ceil(kmer_len / 4) k-mer bytes, most significant first,
+ *               then data_size (counter_size..4) bytes of the clamped count, MOST significant first; no LUT, d_lut_out and view may be NULL. both_strands describes the
+ *               table for the caller's header and changes nothing in the body.
+ * KMC_HIP_EINVAL: a NULL output, kmer_len outside 1..13, no open table (or one of another kmer_len) with d_table == NULL, cutoff_min < 1, cutoff_max < cutoff_min,
+ * counter_size outside 1..4 (counter_max == 1 gives 0), KMC1 with out_lut_prefix_len outside 1..kmer_len or (kmer_len - out_lut_prefix_len) % 4 != 0, KFF with
+ * data_size outside counter_size..4, framing above 1. KMC_HIP_ECAPACITY: out_capacity (bytes) below kept x record bytes — found after the tally, before anything is
+ * written. $KMC_HIP_SMALLK_IPT (1..8, default 8): entries per thread; $KMC_HIP_SMALLK_TALLY_WGS (default 2048): the most workgroups k_sk_tally is launched
+ * with; the result depends on neither. */
+#define KMC_HIP_SPLIT_COVERS_SMALLK_DB 0x109u /* kmc_hip_smallk_tally / _view_device (0x108 stays unknown, as 0x106, 0x104 and 0x101 do) */
+int kmc_hip_smallk_tally(kmc_hip_ctx *ctx, int dev, const uint64_t *d_table, uint32_t kmer_len, uint64_t cutoff_min, uint64_t cutoff_max, uint64_t stats[4]);
+int kmc_hip_smallk_view_device(kmc_hip_ctx *ctx, int dev, const uint64_t *d_table, uint32_t kmer_len, uint32_t both_strands, uint64_t cutoff_min, uint64_t cutoff_max,
+                               uint64_t counter_max, uint32_t framing, uint32_t out_lut_prefix_len, uint32_t data_size, uint8_t *d_out, uint64_t out_capacity,
+                               uint64_t *d_lut_out, kmc_hip_db_view *view, uint64_t *n_kmers, uint64_t stats[4]);
 
 /* ---- stage 0, signature statistics (added within ABI version 4, like kmc_hip_smallk_*) ----
  * The reference decides which signature goes to which bin from a sample of the input: every CWStatsSplitter worker (splitter.h:118, splitter.cpp:878-925) runs

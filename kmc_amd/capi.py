@@ -143,7 +143,7 @@ SYMBOLS = [
     "kmc_hip_debug_expand", "kmc_hip_debug_compact", "kmc_hip_debug_split_reads",
     "kmc_hip_split_reads_plan", "kmc_hip_split_reads_emit", "kmc_hip_split_reads_free",
     "kmc_hip_split_set_map", "kmc_hip_split_part", "kmc_hip_split_covers", "kmc_hip_estimate_open", "kmc_hip_estimate_read", "kmc_hip_estimate_close",
-    "kmc_hip_smallk_open", "kmc_hip_smallk_part", "kmc_hip_smallk_read", "kmc_hip_smallk_close",
+    "kmc_hip_smallk_open", "kmc_hip_smallk_part", "kmc_hip_smallk_read", "kmc_hip_smallk_close", "kmc_hip_smallk_tally", "kmc_hip_smallk_view_device",
     "kmc_hip_sigstats_open", "kmc_hip_sigstats_part", "kmc_hip_sigstats_read", "kmc_hip_sigstats_close", "kmc_hip_sigstats_allowed",
     "kmc_hip_db_set_op_device", "kmc_hip_db_query_reads_device",
     "kmc_hip_db_reduce_device", "kmc_hip_db_histogram_device", "kmc_hip_db_dump_device",
@@ -239,6 +239,7 @@ def load():
         L.kmc_hip_smallk_read.argtypes = [vp, C.c_int, C.c_uint64, C.c_uint64, vp]
         L.kmc_hip_smallk_close.argtypes = [vp, C.c_int]
     bind_sigstats(L)
+    bind_smallk_db(L)
     if hasattr(L, "kmc_hip_db_set_op_device"):  # added within ABI version 4
         L.kmc_hip_db_set_op_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.POINTER(DbView), C.POINTER(DbOp), vp, C.c_uint64, vp, u64p, u64p]
     if hasattr(L, "kmc_hip_db_query_reads_device"):  # added within ABI version 4
@@ -275,6 +276,16 @@ def bind_count(L):
     L.kmc_hip_count_close.argtypes = [vp, vp]
     L.kmc_hip_count_close.restype = None
     L.kmc_hip_debug_gather_segments.argtypes = [vp, C.c_int, vp, vp, vp, C.c_uint64]
+
+
+def bind_smallk_db(L):
+    """the prototypes of the small-k table's road to a database on a loaded library (added within ABI version 4: ask kmc_hip_split_covers(SPLIT_COVERS_SMALLK_DB))"""
+    if not hasattr(L, "kmc_hip_smallk_tally"):
+        return
+    vp = C.c_void_p
+    L.kmc_hip_smallk_tally.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_uint64, C.c_uint64, u64p]
+    L.kmc_hip_smallk_view_device.argtypes = [vp, C.c_int, vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint64, vp,
+                                             C.POINTER(DbView), u64p, u64p]
 
 
 def bind_sigstats(L):
@@ -752,6 +763,93 @@ class SigStats:
     def close(self):
         if self.open:
             self.ctx.L.kmc_hip_sigstats_close(self.ctx.h, self.dev)
+            self.open = False
+
+
+SPLIT_COVERS_SMALLK_DB = 0x109  # KMC_HIP_SPLIT_COVERS_SMALLK_DB
+SMALLK_STATS = ("n_unique", "n_cutoff_min", "n_cutoff_max", "n_kept")  # stats[] of kmc_hip_smallk_tally and kmc_hip_smallk_view_device, in order
+SMALLK_KMC1, SMALLK_KFF = 0, 1  # the framings of kmc_hip_smallk_view_device
+
+
+def counter_size(cutoff_max: int, counter_max: int, L=None) -> int:
+    return int((L or load()).kmc_hip_counter_size(cutoff_max, counter_max))
+
+
+class SmallK:
+    """The small-k table (k <= 13) of one device: reads in part by part (kmc_hip_smallk_open / _part), then the table tallied and framed as a database body or as KFF
+    records where it lies (kmc_hip_smallk_tally / _view_device), or read back (kmc_hip_smallk_read). ctx: a Context, or anything with its L, h, _chk, malloc and free. view() owns
+    the body and the LUT it makes until the next view() or close()."""
+
+    def __init__(self, ctx, k: int, both_strands: bool, dev: int = 0):
+        self.ctx, self.dev, self.k, self.both, self.open, self._bufs = ctx, dev, k, 1 if both_strands else 0, False, []
+        if not hasattr(ctx.L, "kmc_hip_smallk_tally") or ctx.L.kmc_hip_split_covers(SPLIT_COVERS_SMALLK_DB) != 1:
+            raise KmcHipError(-1, f"{lib_path()} has no kmc_hip_smallk_tally")
+        bind_smallk_db(ctx.L)
+        ctx._chk(ctx.L.kmc_hip_smallk_open(ctx.h, dev, k, self.both))
+        self.open = True
+
+    @property
+    def entries(self) -> int:
+        return 1 << (2 * self.k)
+
+    def part_rc(self, text, file_type: int = 1, line_cap: int = SPLIT_LINE_CAP, part_kind: int = 0, flags: int = 0, slot: int = 0):
+        """one part; -> (return code, reads, k-mers counted): the code is 0, UNCOVERED or negative, nothing is raised"""
+        p = SplitParams(self.k, 0, 0, 0, self.both, file_type, line_cap, part_kind, flags)
+        t = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        n_reads, n_kmers = C.c_uint64(0), C.c_uint64(0)
+        rc = self.ctx.L.kmc_hip_smallk_part(self.ctx.h, self.dev, slot, C.byref(p), _vp(t) if t.size else None, t.size, C.byref(n_reads), C.byref(n_kmers))
+        return rc, n_reads.value, n_kmers.value
+
+    def part(self, text, **kw):
+        """one part; -> (reads, k-mers counted). KMC_HIP_UNCOVERED raises like an error: the table is as it was"""
+        rc, n_reads, n_kmers = self.part_rc(text, **kw)
+        if rc == UNCOVERED:
+            raise KmcHipError(rc, "KMC_HIP_UNCOVERED: the part's text is malformed in a way the device splitter does not reproduce")
+        self.ctx._chk(rc)
+        return n_reads, n_kmers
+
+    def read(self, first: int = 0, count: int = None) -> np.ndarray:
+        count = self.entries - first if count is None else count
+        out = np.zeros(max(count, 1), dtype=np.uint64)
+        self.ctx._chk(self.ctx.L.kmc_hip_smallk_read(self.ctx.h, self.dev, first, count, _vp(out)))
+        return out[:count]
+
+    def tally(self, cutoff_min: int, cutoff_max: int, d_table: int = 0) -> dict:
+        """dict of SMALLK_STATS over the open table (or over d_table: 4^k uint64 on the device)"""
+        st = np.zeros(4, dtype=np.uint64)
+        self.ctx._chk(self.ctx.L.kmc_hip_smallk_tally(self.ctx.h, self.dev, d_table or None, self.k, cutoff_min, cutoff_max, st.ctypes.data_as(u64p)))
+        return dict(zip(SMALLK_STATS, (int(x) for x in st)))
+
+    def _malloc(self, nbytes: int) -> int:
+        d = self.ctx.malloc(nbytes, self.dev) if self.dev else self.ctx.malloc(nbytes)
+        self._bufs.append(d)
+        return d
+
+    def _free(self):
+        for b in self._bufs:
+            self.ctx.free(b, self.dev) if self.dev else self.ctx.free(b)
+        self._bufs = []
+
+    def view(self, cutoff_min: int, cutoff_max: int, counter_max: int, lut_prefix_len: int = 0, framing: int = SMALLK_KMC1, data_size: int = 0, d_table: int = 0):
+        """the table as a body on the device, sized by a tally. KMC1 -> (DbView, stats dict): the body and its LUT of 4^lut_prefix_len entries; KFF -> ((device pointer,
+        bytes), stats dict): records of ceil(k / 4) + data_size bytes. The memory is this object's until the next view() or close()."""
+        self._free()
+        kept = self.tally(cutoff_min, cutoff_max, d_table)["n_kept"]
+        cs = counter_size(cutoff_max, counter_max, self.ctx.L)
+        rb = ((self.k + 3) // 4 + data_size) if framing == SMALLK_KFF else (max(self.k - lut_prefix_len, 0) // 4 + cs)
+        cap = kept * rb
+        d_out = self._malloc(cap + 16)
+        d_lut = self._malloc(8 << (2 * min(max(lut_prefix_len, 0), 13))) if framing == SMALLK_KMC1 else 0
+        v, n, st = DbView(), C.c_uint64(0), np.zeros(4, dtype=np.uint64)
+        self.ctx._chk(self.ctx.L.kmc_hip_smallk_view_device(self.ctx.h, self.dev, d_table or None, self.k, self.both, cutoff_min, cutoff_max, counter_max, framing, lut_prefix_len,
+                                                            data_size, d_out, cap, d_lut or None, C.byref(v), C.byref(n), st.ctypes.data_as(u64p)))
+        stats = dict(zip(SMALLK_STATS, (int(x) for x in st)))
+        return ((d_out, n.value * rb) if framing == SMALLK_KFF else v), stats
+
+    def close(self):
+        self._free()
+        if self.open:
+            self.ctx.L.kmc_hip_smallk_close(self.ctx.h, self.dev)
             self.open = False
 
 

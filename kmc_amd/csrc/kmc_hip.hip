@@ -34,6 +34,7 @@
 #include "stage1_kernels.hip.h"
 #include "count_gather.hip.h"
 #include "kff_db.hip.h"
+#include "smallk_db.hip.h"
 
 namespace {
 
@@ -621,3 +622,4 @@ struct DevTemps {
 #include "host_compare.hip.h" /* two ordered databases compared (`kmc_tools compare`) */
 #include "host_kff.hip.h" /* the records of a KFF file imported as a database body (the KFF inputs of every `kmc_tools` database mode) */
 #include "host_kff_export.hip.h" /* a database body framed as the records of a KFF file (KFF output) */
+#include "host_smallk_db.hip.h" /* the small-k table (k <= 13) tallied and framed as a database body or as KFF records (`kmc` with its small-k optimisation, stage 2) */

@@ -1263,8 +1263,8 @@ _COUNT_REFUSED = {"-okff": "KFF output", "-e": "the k-mer number estimation alon
                   "this front end does not read BGZF)", "-fkmc": "KMC-database input", "-sm": "strict memory mode", "-j": "the JSON summary", "-w": "a run without output"}
 
 
-def parse_count(argv) -> dict:
-    """-> dict(k, ci, cx, cs, both, file_type (0 FASTA, 1 FASTQ, 2 multi-line FASTA), hc, m, n_bins, inputs, out)"""
+def _count_options(argv, verb: str, usage: str):
+    """the option loop of `count` and `count-small` (kmc's own grammar) -> (dict(k, ci, cx, cs, both, file_type, hc, m, n_bins), positional arguments)"""
     o = dict(k=25, ci=2, cx=10**9, cs=255, both=True, file_type=1, hc=False, m=None, n_bins=512)
     pos = []
     for a in argv:
@@ -1292,22 +1292,12 @@ def parse_count(argv) -> dict:
             o["file_type"] = {"-fa": 0, "-fq": 1, "-fm": 2}[a]
         else:
             why = next((w for pre, w in _COUNT_REFUSED.items() if a.startswith(pre)), None)
-            raise UsageError(f"count: option {a} is not read" + (f" ({why})" if why else "") + "\n" + COUNT_USAGE)
-    if len(pos) not in (2, 3):
-        raise UsageError(COUNT_USAGE)
-    k = o["k"]
-    if k < 14:
-        raise UsageError(f"count: -k{k}: k <= 13 is counted without bins, by the small-k entries of the library (kmc_hip_smallk_open / _part / _read); this front end takes k 14..224")
-    if k > 224:
-        raise UsageError(f"count: -k{k}: at most 224 (the ordered database's record width)")
-    if o["m"] is None:
-        o["m"] = min(9, k)
-    if not 5 <= o["m"] <= 11:
-        raise UsageError(f"count: -p{o['m']}: the signature length is 5..11")
-    if not 1 <= o["n_bins"] <= 2048:
-        raise UsageError(f"count: -n{o['n_bins']}: 1..2048 bins")
-    if o["ci"] < 1 or o["cs"] < 1 or o["cx"] < o["ci"]:
-        raise UsageError("count: -ci and -cs are at least 1, -cx at least -ci")
+            raise UsageError(f"{verb}: option {a} is not read" + (f" ({why})" if why else "") + "\n" + usage)
+    return o, pos
+
+
+def _count_inputs(o: dict, pos: list) -> dict:
+    """<input | @list> <out> of the command line into o["inputs"], o["out"]"""
     if pos[0].startswith("@"):
         try:
             with open(pos[0][1:]) as f:
@@ -1318,6 +1308,27 @@ def parse_count(argv) -> dict:
         o["inputs"] = [pos[0]]
     o["out"] = pos[1]
     return o
+
+
+def parse_count(argv) -> dict:
+    """-> dict(k, ci, cx, cs, both, file_type (0 FASTA, 1 FASTQ, 2 multi-line FASTA), hc, m, n_bins, inputs, out)"""
+    o, pos = _count_options(argv, "count", COUNT_USAGE)
+    if len(pos) not in (2, 3):
+        raise UsageError(COUNT_USAGE)
+    k = o["k"]
+    if k < 14:
+        raise UsageError(f"count: -k{k}: k <= 13 is counted without bins, by the small-k entries of the library (kmc_hip_smallk_open / _part / _read); this front end takes k 14..224 (`count-small` is the verb for k <= 13)")
+    if k > 224:
+        raise UsageError(f"count: -k{k}: at most 224 (the ordered database's record width)")
+    if o["m"] is None:
+        o["m"] = min(9, k)
+    if not 5 <= o["m"] <= 11:
+        raise UsageError(f"count: -p{o['m']}: the signature length is 5..11")
+    if not 1 <= o["n_bins"] <= 2048:
+        raise UsageError(f"count: -n{o['n_bins']}: 1..2048 bins")
+    if o["ci"] < 1 or o["cs"] < 1 or o["cx"] < o["ci"]:
+        raise UsageError("count: -ci and -cs are at least 1, -cx at least -ci")
+    return _count_inputs(o, pos)
 
 
 def count_signature_map(signature_len: int, n_bins: int, multiplier: int = COUNT_MAP_MULTIPLIER) -> np.ndarray:
@@ -1519,14 +1530,136 @@ def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_
             ctx.close()
 
 
+COUNT_SMALL_USAGE = """usage: python -m kmc_amd.tools count-small [options] <input_file | @file_of_inputs> <out> [<working_dir>]
+  `count` for k <= 13, where `kmc` counts without signatures and bins (its small-k optimisation): -k<len> (1..13, required: kmc's default 25 belongs to `count`)
+  -ci<v> (2) -cx<v> (1e9) -cs<v> (255; at least 2) -b -fa | -fq (default) | -fm -hc. -p* and -n* are accepted and ignored with the options `count` ignores. Writes
+  <out>.kmc_pre / .kmc_suf byte for byte as `kmc` does for such a run (a KMC1 database, ordered as it is); with KMC_HIP_COUNT_OUT=kff <out>.kff as `kmc -okff`
+  followed by `kmc_tools transform <out>.kff reduce <out2> -okff` does."""
+
+
+def parse_count_small(argv) -> dict:
+    """-> dict(k, ci, cx, cs, both, file_type, hc, inputs, out) of a `count-small` command line"""
+    o, pos = _count_options(argv, "count-small", COUNT_SMALL_USAGE)
+    if len(pos) not in (2, 3):
+        raise UsageError(COUNT_SMALL_USAGE)
+    k = o["k"]
+    if not 1 <= k <= 13:
+        raise UsageError(f"count-small: -k{k}: this verb takes k 1..13 (-k is required here); `count` is the verb for k 14..224")
+    if o["ci"] < 1 or o["cs"] < 1 or o["cx"] < o["ci"]:
+        raise UsageError("count-small: -ci and -cs are at least 1, -cx at least -ci")
+    if o["cs"] == 1:
+        raise UsageError("count-small: -cs1 stores no counter bytes at all (counter size 0): the device entries write databases with 1..4 counter bytes")
+    if o["cx"] > 0xFFFFFFFF and o["cs"] > 0xFFFFFFFF:
+        raise UsageError(f"count-small: -cx{o['cx']} with -cs{o['cs']} needs more than four counter bytes; a KMC database record has at most four")
+    return _count_inputs(o, pos)
+
+
+def smallk_lut_prefix_len(k: int, n_unique: int, counter_size: int) -> int:
+    """The LUT prefix length `kmc` picks for a small-k database (ProcessSmallKOptimization_Stage2, kmc.h:906-936): the p in 1..15 with a suffix length (k - p, or 0 for
+    p > k) that is a multiple of 4 and the smallest n_unique x (suffix / 4 + counter_size) + 4^p x 8, the first such p. n_unique: the NON-ZERO entries, before cutoffs."""
+    best, best_mem = 0, 1 << 62
+    for p in range(1, 16):
+        suffix = k - p if p <= k else 0
+        if suffix % 4:
+            continue
+        mem = n_unique * (suffix // 4 + counter_size) + (8 << (2 * p))
+        if mem < best_mem:
+            best, best_mem = p, mem
+    return best
+
+
+COUNT_SMALL_KFF_REFUSED = ()  # the k at which the reference's own KFF pipeline failed while the goldens were recorded (DESIGN.md section 9): none
+
+
+def count_small(argv, ctx=None, part_bytes=None, keep=False, output_format="kmc"):
+    """`kmc` with its small-k optimisation on the device: the reads go through capi.SmallK part by part into the table of 4^k counters, the table is tallied, the LUT
+    prefix length chosen as kmc chooses it, and the table framed as the database body where it lies; only the body and the LUT come down. Returns what `count` returns
+    where it has a meaning: dict(stats = n_unique, n_below_min, n_above_max, n_total; totals = n_reads, n_superkmers (0), n_kmers, bin_bytes (0); n_records, n_parts,
+    file_type); keep=True: (that dict, the open capi.SmallK, its view) — the caller goes on on the device and closes the SmallK (for k <= 4 the view has no suffix bytes and
+    the kmc_hip_db_* entries refuse it). output_format "kff": <out>.kff with data_size = the counter size, min_count = -ci, max_count = -cx, canonical = not -b."""
+    if output_format not in ("kmc", "kff"):
+        raise ValueError(f'count-small: output_format is "kmc" or "kff", not {output_format!r}')
+    o = parse_count_small(argv)
+    k = o["k"]
+    if output_format == "kff" and k in COUNT_SMALL_KFF_REFUSED:
+        raise UsageError(f"count-small: -k{k}: the reference's own KFF pipeline fails at this k; no KFF output")
+    if part_bytes is None:
+        part_bytes = int(os.environ.get("KMC_HIP_COUNT_PART_MB", "0")) << 20 or COUNT_PART_BYTES
+    own = ctx is None
+    if own:
+        ctx = capi.Context((0,))
+    sk = None
+    try:
+        sk = capi.SmallK(ctx, k, o["both"])
+        n_parts = n_reads = n_kmers = 0
+        for path in o["inputs"]:
+            try:
+                for i, part in enumerate(multiline_parts(path, part_bytes) if o["file_type"] == 2 else readsio.parts(path, o["file_type"] == 1, part_bytes)):
+                    try:
+                        r, n = sk.part(part, file_type=o["file_type"], flags=capi.SPLIT_HOMOPOLYMER if o["hc"] else 0)
+                    except capi.KmcHipError as e:
+                        if e.code == capi.UNCOVERED:
+                            raise UsageError(f"count-small: {path}, part {i}: {e}")
+                        raise
+                    n_parts, n_reads, n_kmers = n_parts + 1, n_reads + r, n_kmers + n
+            except OSError as e:
+                raise UsageError(f"cannot open file: {path} ({e.strerror})")
+            except readsio.FormatError as e:
+                raise UsageError(f"count-small: {path}: {e}")
+        tally = sk.tally(o["ci"], o["cx"])
+        cs = capi.counter_size(o["cx"], o["cs"], ctx.L)
+        p_out = smallk_lut_prefix_len(k, tally["n_unique"], cs)
+        view, st = sk.view(o["ci"], o["cx"], o["cs"], p_out)
+        assert st == tally and view.n_recs == tally["n_kept"]
+        if output_format == "kff":
+            (d_kff, n_bytes), st = sk.view(o["ci"], o["cx"], o["cs"], framing=capi.SMALLK_KFF, data_size=cs)
+            recs = np.zeros(n_bytes, dtype=np.uint8)
+            if n_bytes:
+                ctx.d2h(recs, d_kff)
+            dbio.write_kff(o["out"] + ".kff", k, cs, o["both"], o["ci"], o["cx"], [[recs] if n_bytes else []])
+            if keep:
+                view, st = sk.view(o["ci"], o["cx"], o["cs"], p_out)
+        else:
+            _write_smallk_body(ctx, o["out"], k, view, o["ci"], o["cx"], o["both"])
+        res = dict(stats=dict(n_unique=tally["n_unique"], n_below_min=tally["n_cutoff_min"], n_above_max=tally["n_cutoff_max"], n_total=n_kmers),
+                   totals=dict(n_reads=n_reads, n_superkmers=0, n_kmers=n_kmers, bin_bytes=0), n_records=tally["n_kept"], n_parts=n_parts, file_type=o["file_type"])
+        if keep:
+            sk_kept, sk = sk, None
+            return res, sk_kept, view
+        return res
+    finally:
+        if sk is not None:
+            sk.close()
+        if own and not (keep and sk is None):
+            ctx.close()
+
+
+SMALLK_BODY_PART_BYTES = 64 << 20
+
+
+def _write_smallk_body(ctx, path: str, k: int, body: capi.DbView, ci: int, cx: int, both_strands: bool):
+    """_write_body's "kmc1" for a small-k view: the prefix may be the whole k-mer (k <= 4: no suffix bytes), and a large body comes down in parts"""
+    n, p, cs = int(body.n_recs), int(body.lut_prefix_len), int(body.counter_size)
+    if p < k and n * ((k - p) // 4 + cs) <= SMALLK_BODY_PART_BYTES:
+        return _write_body(ctx, "kmc1", path, k, body, ci, cx, both_strands)
+    recs, lut = np.zeros(n * ((k - p) // 4 + cs), dtype=np.uint8), np.zeros(1 << (2 * p), dtype=np.uint64)
+    for at in range(0, recs.size, SMALLK_BODY_PART_BYTES):
+        ctx.d2h(recs[at:at + SMALLK_BODY_PART_BYTES], body.d_recs + at)
+    ctx.d2h(lut, body.d_lut)
+    dbio.write_kmc1(path, k, cs, p, ci, cx, both_strands, lut, recs)
+
+
 def count_report(res: dict) -> str:
-    """the lines of `kmc`'s summary (kmc_CLI/kmc.cpp:410-419) + the bins' balance"""
+    """the lines of `kmc`'s summary (kmc_CLI/kmc.cpp:410-419) + the bins' balance, where the run had bins (`count-small` has none)"""
     s, t = res["stats"], res["totals"]
     rows = [("No. of k-mers below min. threshold", s["n_below_min"]), ("No. of k-mers above max. threshold", s["n_above_max"]), ("No. of unique k-mers", s["n_unique"]),
-            ("No. of unique counted k-mers", s["n_unique"] - s["n_below_min"] - s["n_above_max"]), ("Total no. of k-mers", s["n_total"]), ("Total no. of reads", t["n_reads"]),
-            ("Total no. of super-k-mers", t["n_superkmers"])]
+            ("No. of unique counted k-mers", s["n_unique"] - s["n_below_min"] - s["n_above_max"]), ("Total no. of k-mers", s["n_total"]),
+            ("Total no. of sequences" if res.get("file_type") == 2 else "Total no. of reads", t["n_reads"]), ("Total no. of super-k-mers", t["n_superkmers"])]
+    text = "\n".join("   %-35s: %12d" % r for r in rows)
+    if "balance" not in res:
+        return text
     which = {"fixed": "the fixed signature map", "stats": "the map from stage-0 statistics"}[res.get("map", "fixed")]
-    return "\n".join("   %-35s: %12d" % r for r in rows) + "\n   %-35s: %12.2f  (%s; %d parts, %d segments gathered, %d stage-2 batches)" % (
+    return text + "\n   %-35s: %12.2f  (%s; %d parts, %d segments gathered, %d stage-2 batches)" % (
         "Largest bin / mean bin (k-mers)", res["balance"], which, res["n_parts"], res["n_segments"], res["n_batches"])
 
 
@@ -1535,6 +1668,9 @@ def main(argv=None) -> int:
     if argv and argv[0] == "count":
         print(count_report(count(argv[1:], signature_map="stats" if os.environ.get("KMC_HIP_COUNT_MAP") == "stats" else "fixed",
                                  output_format="kff" if os.environ.get("KMC_HIP_COUNT_OUT") == "kff" else "kmc")))
+        return 0
+    if argv and argv[0] == "count-small":
+        print(count_report(count_small(argv[1:], output_format="kff" if os.environ.get("KMC_HIP_COUNT_OUT") == "kff" else "kmc")))
         return 0
     if argv and argv[0] == "export":
         out = parse_export(argv[1:])[1]["path"]
@@ -1569,7 +1705,7 @@ def main(argv=None) -> int:
         return 0
     if not argv or argv[0] != "simple":
         raise UsageError("usage: python -m kmc_amd.tools simple <db1> [-ci -cx] <db2> [-ci -cx] <operation> <out> [-ci -cx -cs -oc<mode>] ...\n" + FILTER_USAGE + "\n" + TRANSFORM_USAGE + "\n"
-                         + COMPLEX_USAGE + "\n" + COMPARE_USAGE + "\n" + CHECK_USAGE + "\n" + INFO_USAGE + "\n" + COUNT_USAGE + "\n" + EXPORT_USAGE)
+                         + COMPLEX_USAGE + "\n" + COMPARE_USAGE + "\n" + CHECK_USAGE + "\n" + INFO_USAGE + "\n" + COUNT_USAGE + "\n" + COUNT_SMALL_USAGE + "\n" + EXPORT_USAGE)
     for (o, st) in zip(parse_simple(argv[1:])[1], simple(argv[1:])):
         print(f"{o['op']} -> {o['path']}: " + ", ".join(f"{a} {b}" for a, b in st.items()))
     return 0
