@@ -733,6 +733,50 @@ void kmc_hip_count_close(kmc_hip_ctx *ctx, kmc_hip_count *session);
  * [source, source + bytes + 16) of a segment is read. $KMC_HIP_COUNT_GATHER_WGS: workgroups of the persistent grid (default 2048). */
 int kmc_hip_debug_gather_segments(kmc_hip_ctx *ctx, int dev, const uint8_t *d_src, uint8_t *d_dst, const uint64_t *table, uint64_t n_segments);
 
+/* ---- BGZF input: BAM files and bgzipped FASTA / FASTQ inflated on the device (added within ABI version 4) ----
+ * A BGZF file is a sequence of independent gzip members of at most 64 KiB of output each; every member names its own compressed size (BSIZE in the BC extra
+ * subfield) and ends with CRC32 and ISIZE. The host walks the headers, the device inflates one member per wave and checks its CRC (k_bgzf_inflate, bgzf.hip.h).
+ * Ask kmc_hip_split_covers(KMC_HIP_SPLIT_COVERS_BGZF) first. */
+#define KMC_HIP_SPLIT_COVERS_BGZF 0x10Bu /* kmc_hip_bgzf_scan / _inflate_device / _inflate, kmc_hip_bam_whole_records (0x10A stays unknown, as the even values before it do) */
+#define KMC_HIP_BGZF_NONE 0xFFFFFFFFu     /* *first_bad when no member failed */
+typedef struct kmc_hip_bgzf_member {
+	uint64_t src_off;  /* of the member's raw deflate data, in the bytes the table was made from */
+	uint64_t dst_off;  /* of its output: the running sum of the isize fields in front of it */
+	uint32_t comp_len; /* bytes of deflate data: between the gzip header and the 8 bytes of CRC32 and ISIZE */
+	uint32_t isize, crc;
+	uint32_t reserved; /* 0 */
+} kmc_hip_bgzf_member;
+/* Host only, no context. Walks the gzip member headers of src[0 .. size) from byte 0: magic 1f 8b, CM 8, FLG.FEXTRA; the BC subfield of length 2 wherever it lies in
+ * the extra field; FNAME, FCOMMENT and FHCRC skipped where the flags are set. Fills members[0 .. *n_members) and stops in front of the first member that is not wholly
+ * inside `size` (the caller carries src[*src_used ..) to its next piece), that would take the output beyond max_out_bytes, or at `cap` members. *out_bytes = the
+ * members' isize summed. An empty member (the 28-byte EOF block, also in the middle of a file) is an ordinary member of isize 0. KMC_HIP_ECORRUPT, with the byte
+ * offset in the message: a header that is not BGZF, isize above 65536, a BSIZE too small for the member's own header and trailer.
+ * Replaces: the header walk of CFastqReader's BGZF branch (kmc_core/fastq_reader.cpp:72-140). */
+int kmc_hip_bgzf_scan(const uint8_t *src, uint64_t size, uint64_t max_out_bytes, kmc_hip_bgzf_member *members, uint64_t cap, uint64_t *n_members, uint64_t *src_used,
+                      uint64_t *out_bytes);
+/* d_src[0 .. src_size) (device) holds the compressed bytes the table (host memory; uploaded here) was made from; member i's output goes to
+ * d_dst[dst_off, dst_off + isize). Stored, fixed and dynamic blocks, several blocks per member, matches up to length 258 at distance up to 32768. Synchronous; calls on
+ * one (dev, slot) are serialised. Returns 0 with *first_bad = KMC_HIP_BGZF_NONE, or KMC_HIP_ECORRUPT with *first_bad = the smallest failing member, its source offset
+ * and the reason in the message: everything zlib's inflate refuses, output that is not isize bytes, compressed bytes left over or missing, a CRC32 mismatch. A failing
+ * member ends alone: every other member's output is written, a failing member's range is left as it was. member_errors (host, [n_members], may be NULL): 0 or the
+ * reason's number per member. KMC_HIP_ECAPACITY: dst_capacity below the end of the last member's output; KMC_HIP_EINVAL: a NULL argument, a bad slot, a member with
+ * isize or comp_len above 65536, one that ends behind src_size, dst_off values that do not ascend past the output before them. No byte outside a member's compressed
+ * bytes is read and none outside its output range is written, whatever the bytes say.
+ * Replaces: inflate() and crc32() per member on one host thread (kmc_core/fastq_reader.cpp:141-189). */
+int kmc_hip_bgzf_inflate_device(kmc_hip_ctx *ctx, int dev, int slot, const uint8_t *d_src, uint64_t src_size, const kmc_hip_bgzf_member *members, uint64_t n_members,
+                                uint8_t *d_dst, uint64_t dst_capacity, uint32_t *first_bad, uint32_t *member_errors);
+/* the same from host memory to host memory: upload, the device entry's kernel, download (buffers of the slot, grow-only). What `count` uses today; a session entry that
+ * takes device text would spare the two copies (kmc_hip_bgzf_inflate_device exists for it). With KMC_HIP_ECORRUPT the good members' output is in dst all the same.
+ * Replaces: the same lines as kmc_hip_bgzf_inflate_device; CFastqReader::ProcessBamBinaryPart's caller could hand its compressed buffer to this entry. */
+int kmc_hip_bgzf_inflate(kmc_hip_ctx *ctx, int dev, int slot, const uint8_t *src, uint64_t src_size, const kmc_hip_bgzf_member *members, uint64_t n_members, uint8_t *dst,
+                         uint64_t dst_capacity, uint32_t *first_bad, uint32_t *member_errors);
+/* milliseconds between HIP events around the last k_bgzf_inflate of (dev, slot): what tools/bgzf_bench.py reports */
+int kmc_hip_bgzf_last_ms(kmc_hip_ctx *ctx, int dev, int slot, float *ms);
+/* Host only. Walks the block_size chain of inflated BAM alignment records from byte 0 of buf: *n_bytes = the bytes that are whole records (what a part may hold; the
+ * rest is carried in front of the next piece), *n_records = how many. KMC_HIP_ECORRUPT: a block_size below 32 (negative ones included).
+ * Replaces: the record walk of CFastqReader::GetPartFromBam (kmc_core/fastq_reader.cpp:285-361). */
+int kmc_hip_bam_whole_records(const uint8_t *buf, uint64_t size, uint64_t *n_bytes, uint64_t *n_records);
+
 #ifdef __cplusplus
 }
 #endif

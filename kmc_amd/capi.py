@@ -149,6 +149,7 @@ SYMBOLS = [
     "kmc_hip_db_reduce_device", "kmc_hip_db_histogram_device", "kmc_hip_db_dump_device",
     "kmc_hip_db_expr_device", "kmc_hip_kff_import_device", "kmc_hip_db_compare_device", "kmc_hip_db_kff_export_device",
     "kmc_hip_count_open", "kmc_hip_count_part", "kmc_hip_count_finish", "kmc_hip_count_order", "kmc_hip_count_info", "kmc_hip_count_timings", "kmc_hip_count_close", "kmc_hip_debug_gather_segments",
+    "kmc_hip_bgzf_scan", "kmc_hip_bgzf_inflate_device", "kmc_hip_bgzf_inflate", "kmc_hip_bgzf_last_ms", "kmc_hip_bam_whole_records",
 ]
 
 _LIB = None
@@ -257,6 +258,7 @@ def load():
     if hasattr(L, "kmc_hip_db_kff_export_device"):  # added within ABI version 4
         L.kmc_hip_db_kff_export_device.argtypes = [vp, C.c_int, C.c_uint32, C.POINTER(DbView), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, vp, C.c_uint64]
     bind_count(L)
+    bind_bgzf(L)
     _LIB = L
     return L
 
@@ -851,6 +853,103 @@ class SmallK:
         if self.open:
             self.ctx.L.kmc_hip_smallk_close(self.ctx.h, self.dev)
             self.open = False
+
+
+# ---- BGZF input (BAM, bgzipped FASTA / FASTQ): the member table on the host, the members inflated on the device
+SPLIT_COVERS_BGZF = 0x10B  # KMC_HIP_SPLIT_COVERS_BGZF: kmc_hip_bgzf_scan / _inflate_device / _inflate, kmc_hip_bam_whole_records (0x10A stays unknown)
+BGZF_NONE = 0xFFFFFFFF  # KMC_HIP_BGZF_NONE
+BGZF_MEMBER = np.dtype([("src_off", "<u8"), ("dst_off", "<u8"), ("comp_len", "<u4"), ("isize", "<u4"), ("crc", "<u4"), ("reserved", "<u4")])  # struct kmc_hip_bgzf_member
+BGZF_REASONS = ("", "btype", "stored", "codeset", "no_eob", "repeat", "symbol", "distance", "out_short", "out_long", "in_left", "in_short", "crc", "table")  # member_errors values
+
+
+def bind_bgzf(L):
+    """the prototypes of the BGZF entries on a loaded library (added within ABI version 4: ask kmc_hip_split_covers(SPLIT_COVERS_BGZF))"""
+    if not hasattr(L, "kmc_hip_bgzf_scan"):
+        return
+    vp = C.c_void_p
+    L.kmc_hip_last_error.argtypes = [vp]
+    L.kmc_hip_last_error.restype = C.c_char_p
+    L.kmc_hip_bgzf_scan.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, u64p, u64p, u64p]
+    L.kmc_hip_bgzf_inflate_device.argtypes = [vp, C.c_int, C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint32), vp]
+    L.kmc_hip_bgzf_inflate.argtypes = [vp, C.c_int, C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint32), vp]
+    L.kmc_hip_bgzf_last_ms.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.kmc_hip_bam_whole_records.argtypes = [vp, C.c_uint64, u64p, u64p]
+
+
+class BgzfError(KmcHipError):
+    """KMC_HIP_ECORRUPT of an inflate call: .first_bad the smallest failing member, .member_errors the reason's number per member, .out what the other members wrote"""
+
+    def __init__(self, code, msg, first_bad, member_errors, out):
+        super().__init__(code, msg)
+        self.first_bad, self.member_errors, self.out = first_bad, member_errors, out
+
+
+def _bgzf_lib(L):
+    L = L or load()
+    if not hasattr(L, "kmc_hip_bgzf_scan"):
+        raise KmcHipError(-1, f"{lib_path()} has no kmc_hip_bgzf_scan")
+    bind_bgzf(L)
+    return L
+
+
+def _u8(a) -> np.ndarray:
+    return np.frombuffer(a, dtype=np.uint8) if isinstance(a, (bytes, bytearray, memoryview)) else np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def bgzf_scan(src, max_out_bytes: int = 1 << 62, cap: int = None, L=None):
+    """kmc_hip_bgzf_scan -> (members: BGZF_MEMBER array, bytes of src the members take, inflated bytes). Host only."""
+    L = _bgzf_lib(L)
+    s = _u8(src)
+    cap = s.size // 26 + 1 if cap is None else cap  # a member is at least 26 bytes
+    members = np.zeros(max(cap, 1), dtype=BGZF_MEMBER)
+    n, used, out = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = L.kmc_hip_bgzf_scan(_vp(s) if s.size else None, s.size, max_out_bytes, _vp(members), cap, C.byref(n), C.byref(used), C.byref(out))
+    if rc:
+        raise KmcHipError(rc, L.kmc_hip_last_error(None).decode())
+    return members[:n.value], used.value, out.value
+
+
+def bgzf_inflate(ctx, src, members: np.ndarray, dst_capacity: int = None, dev: int = 0, slot: int = 0) -> np.ndarray:
+    """kmc_hip_bgzf_inflate: the members of the table out of src (host bytes) -> the inflated bytes (uint8 array of the table's total, or of dst_capacity).
+    ctx: a Context, or anything with its L and h. A refused member raises BgzfError."""
+    L = _bgzf_lib(ctx.L)
+    s, members = _u8(src), np.ascontiguousarray(members, dtype=BGZF_MEMBER)
+    total = int(members["dst_off"][-1] + members["isize"][-1]) if members.size else 0
+    cap = total if dst_capacity is None else dst_capacity
+    out, errs, bad = np.zeros(max(cap, 1), dtype=np.uint8), np.zeros(max(members.size, 1), dtype=np.uint32), C.c_uint32(BGZF_NONE)
+    rc = L.kmc_hip_bgzf_inflate(ctx.h, dev, slot, _vp(s) if s.size else None, s.size, _vp(members) if members.size else None, members.size, _vp(out), cap, C.byref(bad), _vp(errs))
+    if rc:
+        msg = L.kmc_hip_last_error(ctx.h).decode()
+        if bad.value != BGZF_NONE:
+            raise BgzfError(rc, msg, bad.value, errs[:members.size], out[:cap])
+        raise KmcHipError(rc, msg)
+    return out[:cap]
+
+
+def bgzf_inflate_device(ctx, d_src: int, src_size: int, members: np.ndarray, d_dst: int, dst_capacity: int, dev: int = 0, slot: int = 0) -> float:
+    """kmc_hip_bgzf_inflate_device on device pointers; -> the kernel's milliseconds (HIP events). A refused member raises BgzfError (out=None)."""
+    L = _bgzf_lib(ctx.L)
+    members = np.ascontiguousarray(members, dtype=BGZF_MEMBER)
+    errs, bad, ms = np.zeros(max(members.size, 1), dtype=np.uint32), C.c_uint32(BGZF_NONE), C.c_float(0)
+    rc = L.kmc_hip_bgzf_inflate_device(ctx.h, dev, slot, d_src or None, src_size, _vp(members) if members.size else None, members.size, d_dst or None, dst_capacity, C.byref(bad), _vp(errs))
+    if rc:
+        msg = L.kmc_hip_last_error(ctx.h).decode()
+        if bad.value != BGZF_NONE:
+            raise BgzfError(rc, msg, bad.value, errs[:members.size], None)
+        raise KmcHipError(rc, msg)
+    L.kmc_hip_bgzf_last_ms(ctx.h, dev, slot, C.byref(ms))
+    return float(ms.value)
+
+
+def bam_whole_records(buf, L=None):
+    """kmc_hip_bam_whole_records -> (bytes of buf that are whole BAM alignment records, how many records). Host only."""
+    L = _bgzf_lib(L)
+    b = _u8(buf)
+    n_bytes, n_recs = C.c_uint64(0), C.c_uint64(0)
+    rc = L.kmc_hip_bam_whole_records(_vp(b) if b.size else None, b.size, C.byref(n_bytes), C.byref(n_recs))
+    if rc:
+        raise KmcHipError(rc, L.kmc_hip_last_error(None).decode())
+    return n_bytes.value, n_recs.value
 
 
 # ---- synthetic stage-2 inputs (libkmc_synth.so)

@@ -280,7 +280,7 @@ int kmc_hip_split_set_map(kmc_hip_ctx *ctx, int dev, const int32_t *sig_to_bin, 
 int kmc_hip_split_covers(uint32_t what)
 {
 	return what <= 2 || what == 4 || what == KMC_HIP_SPLIT_COVERS_HOMOPOLYMER || what == KMC_HIP_SPLIT_COVERS_ESTIMATE || what == KMC_HIP_SPLIT_COVERS_SMALLK ||
-	               what == KMC_HIP_SPLIT_COVERS_COUNT || what == KMC_HIP_SPLIT_COVERS_SIGSTATS || what == KMC_HIP_SPLIT_COVERS_SMALLK_DB
+	               what == KMC_HIP_SPLIT_COVERS_COUNT || what == KMC_HIP_SPLIT_COVERS_SIGSTATS || what == KMC_HIP_SPLIT_COVERS_SMALLK_DB || what == KMC_HIP_SPLIT_COVERS_BGZF
 	           ? 1
 	           : 0;
 }

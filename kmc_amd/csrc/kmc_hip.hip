@@ -35,6 +35,7 @@
 #include "count_gather.hip.h"
 #include "kff_db.hip.h"
 #include "smallk_db.hip.h"
+#include "bgzf.hip.h"
 
 namespace {
 
@@ -216,6 +217,8 @@ struct Slot {
 	DBuf recA, recB, recC, pairA, pairB, zero, dbase, out, lut, sticky;
 	DBuf bounds;   /* hybrid sort: tile boundaries of k_bucket_bounds, u64[windows + 1] */
 	DBuf arena_work; /* rank groups of one-word records: entries, offsets, bucket numbers, heavy chunks, digit bases and look-back rows of the arena's passes (the arenas: pairA / pairB) */
+	DBuf bgzf_src, bgzf_dst, bgzf_work; /* BGZF (host_bgzf.hip.h): the compressed bytes and the inflated ones of the host-to-host entry; the member table, the error words and the smallest failing member */
+	float bgzf_ms = 0; /* HIP events around the last k_bgzf_inflate of this slot */
 	DBuf redo_log; /* hybrid sort: one "sort me again" word per asynchronous group since the last drain (drain_redo) */
 	/* pinned staging for callers whose buffers are ordinary (pageable) memory — the drop-in worker's arena: a copy straight from / to such memory makes the
 	 * runtime pin the caller's pages on the fly, and the unmapping of an arena that has been pinned piecewise costs twice as much at the end of KMC's stage 2
@@ -392,7 +395,7 @@ int slot_init(Slot &s, u64 portion)
 
 void slot_destroy(Slot &s)
 {
-	for (DBuf *b : {&s.in, &s.pack_start, &s.recA, &s.recB, &s.recC, &s.pairA, &s.pairB, &s.zero, &s.dbase, &s.out, &s.lut, &s.sticky, &s.bounds, &s.arena_work, &s.redo_log, &s.hb_res})
+	for (DBuf *b : {&s.in, &s.pack_start, &s.recA, &s.recB, &s.recC, &s.pairA, &s.pairB, &s.zero, &s.dbase, &s.out, &s.lut, &s.sticky, &s.bounds, &s.arena_work, &s.redo_log, &s.hb_res, &s.bgzf_src, &s.bgzf_dst, &s.bgzf_work})
 		if (b->p && !b->carved)
 			(void)hipFree(b->p);
 	if (s.slab.p)
@@ -623,3 +626,4 @@ struct DevTemps {
 #include "host_kff.hip.h" /* the records of a KFF file imported as a database body (the KFF inputs of every `kmc_tools` database mode) */
 #include "host_kff_export.hip.h" /* a database body framed as the records of a KFF file (KFF output) */
 #include "host_smallk_db.hip.h" /* the small-k table (k <= 13) tallied and framed as a database body or as KFF records (`kmc` with its small-k optimisation, stage 2) */
+#include "host_bgzf.hip.h" /* BGZF members inflated on the device (BAM and bgzipped reads for `count`), the member table and the cut of BAM text into whole records on the host */

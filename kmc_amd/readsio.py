@@ -7,6 +7,7 @@ its line end. Line ends are '\\n' or '\\r\\n'."""
 from __future__ import annotations
 
 import gzip
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -96,18 +97,137 @@ def sequence_buffer(rec: Records):
     return buf, off
 
 
-def parts(path: str, fastq: bool, part_bytes: int):
-    """yields the file's text in parts of whole records of about part_bytes"""
-    rest = np.zeros(0, dtype=np.uint8)
-    with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
+def is_bgzf(path: str) -> bool:
+    """the file's first gzip member has the BC subfield of length 2 in its extra field: BGZF (BAM, bgzip), not plain gzip"""
+    with open(path, "rb") as f:
+        h = f.read(12)
+        if len(h) < 12 or h[:3] != b"\x1f\x8b\x08" or not h[3] & 4:
+            return False
+        extra = f.read(h[10] | h[11] << 8)
+    x = 0
+    while x + 4 <= len(extra):
+        slen = extra[x + 2] | extra[x + 3] << 8
+        if extra[x:x + 2] == b"BC" and slen == 2 and x + 6 <= len(extra):
+            return True
+        x += 4 + slen
+    return False
+
+
+def on_device(path: str, ctx) -> bool:
+    """do this file's bytes come from the device inflate? a context is given, $KMC_HIP_BGZF is not 0 and the file is BGZF"""
+    return ctx is not None and os.environ.get("KMC_HIP_BGZF", "1") != "0" and is_bgzf(path)
+
+
+def bgzf_chunks(path: str, ctx, part_bytes: int, piece_bytes: int = None):
+    """A BGZF file's inflated bytes as uint8 arrays of about part_bytes, inflated on the device (capi.bgzf_inflate): the file is read in compressed pieces
+    ($KMC_HIP_BGZF_PIECE bytes, by default a quarter of part_bytes), each piece's member table comes from capi.bgzf_scan, the incomplete last member is carried in
+    front of the next piece. A member that is not BGZF, a member the device refuses and a file that ends inside a member raise FormatError with the file offset."""
+    from . import capi
+
+    if piece_bytes is None:
+        piece_bytes = int(os.environ.get("KMC_HIP_BGZF_PIECE", "0")) or max(part_bytes // 4, 1 << 16)
+    carry, base = np.zeros(0, dtype=np.uint8), 0  # base: the file offset of carry[0]
+    with open(path, "rb") as f:
+        while True:
+            piece = f.read(piece_bytes)
+            buf = np.concatenate([carry, np.frombuffer(piece, dtype=np.uint8)]) if carry.size else np.frombuffer(piece, dtype=np.uint8)
+            pos = 0
+            while pos < buf.size:
+                try:
+                    members, used, out_bytes = capi.bgzf_scan(buf[pos:], part_bytes, L=ctx.L)
+                    if not members.size:  # a member of more than part_bytes (it holds at most 64 KiB) goes alone
+                        members, used, out_bytes = capi.bgzf_scan(buf[pos:], 1 << 16, cap=1, L=ctx.L)
+                except capi.KmcHipError as e:
+                    msg, _, at = str(e).rpartition(" at byte ")
+                    raise FormatError(f"BGZF: {msg.split(': ', 2)[-1]} at byte {base + pos + int(at)} of the file")
+                if not members.size:
+                    break
+                try:
+                    out = capi.bgzf_inflate(ctx, buf[pos:pos + used], members)
+                    if out.size:
+                        yield out
+                except capi.BgzfError as e:
+                    raise FormatError(f"BGZF: the member whose compressed data starts at byte {base + pos + int(members['src_off'][e.first_bad])} of the file is corrupt: "
+                                      + str(e).rpartition("): ")[2])
+                pos += used
+            carry, base = buf[pos:], base + pos
+            if not piece:
+                break
+    if carry.size:
+        raise FormatError(f"BGZF: the file ends inside the member at byte {base}")
+
+
+def chunks(path: str, part_bytes: int, ctx=None, gz: bool = None):
+    """the file's (inflated) bytes as uint8 arrays of about part_bytes: from the device where on_device() says so, else through gzip (gz, by default a name that ends
+    in .gz) or as they are"""
+    if on_device(path, ctx):
+        yield from bgzf_chunks(path, ctx, part_bytes)
+        return
+    with (gzip.open(path, "rb") if (path.endswith(".gz") if gz is None else gz) else open(path, "rb")) as f:
         while True:
             chunk = f.read(part_bytes)
             if not chunk:
                 break
-            buf = np.concatenate([rest, np.frombuffer(chunk, dtype=np.uint8)])
-            n = whole_records(buf, fastq)
-            if n:
-                yield buf[:n]
-            rest = buf[n:]
+            yield np.frombuffer(chunk, dtype=np.uint8)
+
+
+def parts(path: str, fastq: bool, part_bytes: int, ctx=None):
+    """yields the file's text in parts of whole records of about part_bytes. ctx (a capi.Context, or anything with its L and h): a BGZF file is inflated on the device"""
+    rest = np.zeros(0, dtype=np.uint8)
+    for chunk in chunks(path, part_bytes, ctx):
+        buf = np.concatenate([rest, chunk])
+        n = whole_records(buf, fastq)
+        if n:
+            yield buf[:n]
+        rest = buf[n:]
     if rest.size:
         yield rest  # no whole record: parse() says what is wrong with it
+
+
+def bam_parts(path: str, part_bytes: int, ctx):
+    """A BAM file as the reference's BAM reader hands it to the splitter (CFastqReader::GetPartFromBam, kmc_core/fastq_reader.cpp:191-362): the inflated stream without
+    its header (magic, l_text, text, n_ref, references — over however many members), in parts of whole alignment records (capi.bam_whole_records); what is left of
+    a record goes in front of the next chunk. No magic, a damaged block_size and a stream that ends inside the header or a record raise FormatError."""
+    from . import capi
+
+    def header_bytes(b):
+        """the header's length, or None while b does not hold all of it"""
+        if b.size < 12:
+            return None
+        at = 8 + int(b[4:8].view("<i4")[0])
+        if at < 8:
+            raise FormatError("BAM: negative l_text")
+        if b.size < at + 4:
+            return None
+        n_ref = int(b[at:at + 4].view("<i4")[0])
+        at += 4
+        for _ in range(max(n_ref, 0)):
+            if b.size < at + 4:
+                return None
+            l_name = int(b[at:at + 4].view("<i4")[0])
+            if l_name < 0:
+                raise FormatError("BAM: negative l_name")
+            at += 4 + l_name + 4
+        return at if b.size >= at else None
+
+    buf, in_header = np.zeros(0, dtype=np.uint8), True
+    for chunk in chunks(path, part_bytes, ctx, gz=True):
+        buf = np.concatenate([buf, chunk]) if buf.size else chunk
+        if in_header:
+            if buf.size >= 4 and buf[:4].tobytes() != b"BAM\1":
+                raise FormatError("BAM: the inflated stream does not start with the magic BAM\\1")
+            n = header_bytes(np.ascontiguousarray(buf))
+            if n is None:
+                continue
+            buf, in_header = buf[n:], False
+        try:
+            n, _ = capi.bam_whole_records(buf, L=ctx.L)
+        except capi.KmcHipError as e:
+            raise FormatError("BAM: " + str(e).split(": ", 2)[-1])
+        if n:
+            yield buf[:n]
+        buf = buf[n:]
+    if in_header:
+        raise FormatError("BAM: the stream ends inside the header" if buf.size >= 4 else "BAM: the inflated stream does not start with the magic BAM\\1")
+    if buf.size:
+        raise FormatError(f"BAM: the stream ends inside a record ({buf.size} bytes left over)")

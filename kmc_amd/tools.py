@@ -462,8 +462,12 @@ def filter_reads(argv, ctx=None) -> dict:
         view = dev.view(ci, cx)
         with open(o["out"], "wb") as out:
             for path in o["inputs"]:
-                for text in readsio.parts(path, o["in_fastq"], part_bytes):
+                parts = readsio.parts(path, o["in_fastq"], part_bytes, ctx)
+                while True:
                     try:
+                        text = next(parts, None)  # a BGZF input is inflated on the device; what breaks in it is named here
+                        if text is None:
+                            break
                         data, n_in, n_out, st = _filter_part(ctx, view, db.kmer_len, db.both_strands, o, text)
                     except readsio.FormatError as e:
                         raise UsageError(f"{path}: {e}")
@@ -1256,11 +1260,13 @@ COUNT_USAGE = """usage: python -m kmc_amd.tools count [options] <input_file | @f
   the argument order of `kmc`, so a kmc command line carries over. Read: -k<len> (25; 14..224) -ci<v> (2) -cx<v> (1e9) -cs<v> (255) -b -fa | -fq (default) | -fm -hc
   -p<signature_len> (min(9, k); 5..11) -n<bins> (512; at most 2048). Accepted and ignored (they size the reference's host pipeline): -t* -m* -r -sf* -sp* -sr* -v and
   <working_dir>. Everything else is refused. Writes <out>.kmc_pre / .kmc_suf as `kmc` followed by `kmc_tools transform <db> sort <out>` does; with
-  KMC_HIP_COUNT_OUT=kff in the environment <out>.kff instead, as `kmc -okff` followed by `kmc_tools transform <out>.kff reduce <out2> -okff` does."""
+  KMC_HIP_COUNT_OUT=kff in the environment <out>.kff instead, as `kmc -okff` followed by `kmc_tools transform <out>.kff reduce <out2> -okff` does.
+  A bgzipped input (BGZF: what `bgzip` writes) is recognised by its content and inflated on the device; plain gzip is inflated on the host. With KMC_HIP_COUNT_IN=bam
+  in the environment the inputs are BAM files (what `kmc -fbam` reads); -fa / -fq / -fm are then refused."""
 COUNT_PART_BYTES = 32 << 20
 COUNT_MAP_MULTIPLIER = 0x9E3779B1
-_COUNT_REFUSED = {"-okff": "KFF output", "-e": "the k-mer number estimation alone", "--opt-out-size": "the output size optimisation", "-fbam": "BAM input (the session entry takes BAM parts; "
-                  "this front end does not read BGZF)", "-fkmc": "KMC-database input", "-sm": "strict memory mode", "-j": "the JSON summary", "-w": "a run without output"}
+_COUNT_REFUSED = {"-okff": "KFF output", "-e": "the k-mer number estimation alone", "--opt-out-size": "the output size optimisation", "-fbam": "BAM input is chosen with "
+                  "KMC_HIP_COUNT_IN=bam in the environment or input_format=\"bam\" of tools.count / tools.count_small, not with this option yet", "-fkmc": "KMC-database input", "-sm": "strict memory mode", "-j": "the JSON summary", "-w": "a run without output"}
 
 
 def _count_options(argv, verb: str, usage: str):
@@ -1401,13 +1407,29 @@ def balanced_signature_map(stats: np.ndarray, signature_len: int, n_bins: int, a
     return out
 
 
+def _input_format(verb: str, input_format, argv) -> bool:
+    """is the input BAM? input_format: None / "reads" (what the options say) or "bam", which the file-type options contradict"""
+    if input_format not in (None, "reads", "bam"):
+        raise ValueError(f'{verb}: input_format is "reads" or "bam", not {input_format!r}')
+    if input_format == "bam" and any(a in ("-fa", "-fq", "-fm") for a in argv):
+        raise UsageError(f"{verb}: BAM input and {next(a for a in argv if a in ('-fa', '-fq', '-fm'))} contradict each other")
+    return input_format == "bam"
+
+
+def _count_parts(o: dict, path: str, part_bytes: int, ctx):
+    """the parts of one input file as the session takes them under o["file_type"]; a BGZF file is inflated on the device"""
+    if o["file_type"] == capi.SPLIT_FILE_BAM:
+        return readsio.bam_parts(path, part_bytes, ctx)
+    return multiline_parts(path, part_bytes, ctx) if o["file_type"] == 2 else readsio.parts(path, o["file_type"] == 1, part_bytes, ctx)
+
+
 def count_stats_sample(ctx, o: dict, part_bytes: int) -> np.ndarray:
     """stage 0 of `count`: the first part of every input file through a capi.SigStats accumulator -> the statistics, uint32[4^m + 1]"""
     acc = capi.SigStats(ctx, o["k"], o["m"])
     try:
         for path in o["inputs"]:
             try:
-                part = next(iter(multiline_parts(path, part_bytes) if o["file_type"] == 2 else readsio.parts(path, o["file_type"] == 1, part_bytes)), None)
+                part = next(iter(_count_parts(o, path, part_bytes, ctx)), None)
             except OSError as e:
                 raise UsageError(f"cannot open file: {path} ({e.strerror})")
             except readsio.FormatError as e:
@@ -1425,10 +1447,10 @@ def count_stats_sample(ctx, o: dict, part_bytes: int) -> np.ndarray:
         acc.close()
 
 
-def multiline_parts(path: str, part_bytes: int):
+def multiline_parts(path: str, part_bytes: int, ctx=None):
     """A multi-line FASTA file in parts as the reference's reader hands them to the splitter (CFastqReader::GetPartFromMultilneFasta, fastq_reader.cpp:399-468): a title
-    keeps its line end, the sequence lines lose theirs. Parts are cut in front of a '>' at a line start; a record longer than part_bytes makes its part longer."""
-    import gzip
+    keeps its line end, the sequence lines lose theirs. Parts are cut in front of a '>' at a line start; a record longer than part_bytes makes its part longer.
+    ctx: a BGZF file is inflated on the device (readsio.chunks)."""
 
     def strip(buf):
         if not buf.size:
@@ -1440,28 +1462,23 @@ def multiline_parts(path: str, part_bytes: int):
         return buf[keep]
 
     held, last = [], 10  # the chunks of the part that is growing (joined once, when a cut is found: a sequence far longer than a part costs one copy), the byte before the next chunk
-    with (gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")) as f:
-        while True:
-            chunk = f.read(part_bytes)
-            if not chunk:
-                break
-            c = np.frombuffer(chunk, dtype=np.uint8)
-            at = np.flatnonzero((c[1:] == 62) & (c[:-1] == 10)) + 1  # a '>' at a line start
-            n = int(at[-1]) if at.size else (0 if held and last == 10 and c[0] == 62 else -1)
-            last = int(c[-1])
-            if n < 0 or (n == 0 and not held):
-                held.append(c)
-                continue
-            buf = np.concatenate(held + [c[:n]]) if held or n < c.size else c
-            if buf.size:
-                yield strip(buf)
-            held = [c[n:]]
+    for c in readsio.chunks(path, part_bytes, ctx):
+        at = np.flatnonzero((c[1:] == 62) & (c[:-1] == 10)) + 1  # a '>' at a line start
+        n = int(at[-1]) if at.size else (0 if held and last == 10 and c[0] == 62 else -1)
+        last = int(c[-1])
+        if n < 0 or (n == 0 and not held):
+            held.append(c)
+            continue
+        buf = np.concatenate(held + [c[:n]]) if held or n < c.size else c
+        if buf.size:
+            yield strip(buf)
+        held = [c[n:]]
     rest = np.concatenate(held) if held else np.zeros(0, dtype=np.uint8)
     if rest.size:
         yield strip(rest)
 
 
-def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_MULTIPLIER, signature_map="fixed", output_format="kmc"):
+def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_MULTIPLIER, signature_map="fixed", output_format="kmc", input_format=None):
     """`kmc` + `kmc_tools transform sort` on the device: the reads of the input files go through a counting session (capi.CountSession) part by part, the ordered body is
     written as a KMC1 database. Returns dict(stats = the four tallies of stage 2 by name, totals = reads, super-k-mers, k-mers, bytes of bin records, n_records, n_parts,
     n_segments, n_batches, balance = k-mers of the largest bin / of the mean bin, map = the signature map that ran); keep=True: (that dict, the open session, its view) —
@@ -1469,12 +1486,17 @@ def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_
     signature_map: "fixed" = count_signature_map's spread; "stats" = stage 0 first: the first part of every input file through capi.SigStats, the map from
     balanced_signature_map. With fewer than COUNT_MAP_MIN_BINS bins "stats" keeps the fixed map and the result says so. The database does not depend on the map.
     output_format: "kmc" = <out>.kmc_pre / .kmc_suf; "kff" = <out>.kff as `kmc -okff` followed by `kmc_tools transform <out>.kff reduce <out2> -okff` writes it (one
-    ordered section, min_count = -ci, max_count = -cx, canonical = not -b): the session's view goes to kmc_hip_db_kff_export_device and only KFF bytes come down."""
+    ordered section, min_count = -ci, max_count = -cx, canonical = not -b): the session's view goes to kmc_hip_db_kff_export_device and only KFF bytes come down.
+    input_format: "bam" = the inputs are BAM files, as for `kmc -fbam`: BGZF inflated on the device (kmc_hip_bgzf_inflate), the header taken off, parts of whole
+    alignment records to the session with file_type 4. A bgzipped FASTA / FASTQ is recognised by its content and needs no option."""
     if signature_map not in ("fixed", "stats"):
         raise ValueError(f'count: signature_map is "fixed" or "stats", not {signature_map!r}')
     if output_format not in ("kmc", "kff"):
         raise ValueError(f'count: output_format is "kmc" or "kff", not {output_format!r}')
+    bam = _input_format("count", input_format, argv)
     o = parse_count(argv)
+    if bam:
+        o["file_type"] = capi.SPLIT_FILE_BAM
     if part_bytes is None:
         part_bytes = int(os.environ.get("KMC_HIP_COUNT_PART_MB", "0")) << 20 or COUNT_PART_BYTES
     k = o["k"]
@@ -1495,7 +1517,7 @@ def count(argv, ctx=None, part_bytes=None, keep=False, map_multiplier=COUNT_MAP_
         n_parts = 0
         for path in o["inputs"]:
             try:
-                for i, part in enumerate(multiline_parts(path, part_bytes) if o["file_type"] == 2 else readsio.parts(path, o["file_type"] == 1, part_bytes)):
+                for i, part in enumerate(_count_parts(o, path, part_bytes, ctx)):
                     try:
                         ses.part(part, p)
                     except capi.KmcHipError as e:
@@ -1571,7 +1593,7 @@ def smallk_lut_prefix_len(k: int, n_unique: int, counter_size: int) -> int:
 COUNT_SMALL_KFF_REFUSED = ()  # the k at which the reference's own KFF pipeline failed while the goldens were recorded: none
 
 
-def count_small(argv, ctx=None, part_bytes=None, keep=False, output_format="kmc"):
+def count_small(argv, ctx=None, part_bytes=None, keep=False, output_format="kmc", input_format=None):
     """`kmc` with its small-k optimisation on the device: the reads go through capi.SmallK part by part into the table of 4^k counters, the table is tallied, the LUT
     prefix length chosen as kmc chooses it, and the table framed as the database body where it lies; only the body and the LUT come down. Returns what `count` returns
     where it has a meaning: dict(stats = n_unique, n_below_min, n_above_max, n_total; totals = n_reads, n_superkmers (0), n_kmers, bin_bytes (0); n_records, n_parts,
@@ -1579,7 +1601,10 @@ def count_small(argv, ctx=None, part_bytes=None, keep=False, output_format="kmc"
     the kmc_hip_db_* entries refuse it). output_format "kff": <out>.kff with data_size = the counter size, min_count = -ci, max_count = -cx, canonical = not -b."""
     if output_format not in ("kmc", "kff"):
         raise ValueError(f'count-small: output_format is "kmc" or "kff", not {output_format!r}')
+    bam = _input_format("count-small", input_format, argv)
     o = parse_count_small(argv)
+    if bam:
+        o["file_type"] = capi.SPLIT_FILE_BAM
     k = o["k"]
     if output_format == "kff" and k in COUNT_SMALL_KFF_REFUSED:
         raise UsageError(f"count-small: -k{k}: the reference's own KFF pipeline fails at this k; no KFF output")
@@ -1594,7 +1619,7 @@ def count_small(argv, ctx=None, part_bytes=None, keep=False, output_format="kmc"
         n_parts = n_reads = n_kmers = 0
         for path in o["inputs"]:
             try:
-                for i, part in enumerate(multiline_parts(path, part_bytes) if o["file_type"] == 2 else readsio.parts(path, o["file_type"] == 1, part_bytes)):
+                for i, part in enumerate(_count_parts(o, path, part_bytes, ctx)):
                     try:
                         r, n = sk.part(part, file_type=o["file_type"], flags=capi.SPLIT_HOMOPOLYMER if o["hc"] else 0)
                     except capi.KmcHipError as e:
@@ -1667,10 +1692,12 @@ def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     if argv and argv[0] == "count":
         print(count_report(count(argv[1:], signature_map="stats" if os.environ.get("KMC_HIP_COUNT_MAP") == "stats" else "fixed",
-                                 output_format="kff" if os.environ.get("KMC_HIP_COUNT_OUT") == "kff" else "kmc")))
+                                 output_format="kff" if os.environ.get("KMC_HIP_COUNT_OUT") == "kff" else "kmc",
+                                 input_format="bam" if os.environ.get("KMC_HIP_COUNT_IN") == "bam" else None)))
         return 0
     if argv and argv[0] == "count-small":
-        print(count_report(count_small(argv[1:], output_format="kff" if os.environ.get("KMC_HIP_COUNT_OUT") == "kff" else "kmc")))
+        print(count_report(count_small(argv[1:], output_format="kff" if os.environ.get("KMC_HIP_COUNT_OUT") == "kff" else "kmc",
+                                       input_format="bam" if os.environ.get("KMC_HIP_COUNT_IN") == "bam" else None)))
         return 0
     if argv and argv[0] == "export":
         out = parse_export(argv[1:])[1]["path"]
